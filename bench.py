@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: sampler it/s of the txt2img hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config NAME]
+    python bench.py --gpus N --steps K --warmup W [--config NAME] [--dump-outputs DIR] [--full]
 
 N > 1: one rank per GPU over RCCL.  Either the caller launches the ranks (`python -m torch.distributed.run --nproc-per-node N ... bench.py
 --gpus N`, what the driver does: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* come from the environment) or, when WORLD_SIZE is not set,
@@ -18,9 +18,18 @@ Workloads (--config; `config.workload` names the one that ran; BASELINE.json `co
 Random-init weights and synthetic conditioning (no checkpoints / datasets here).  A "step" is one sampler iteration through the Forge
 call surface: CFGDenoiser.forward -> sampling_function -> KModel (pack, network forward, prediction -> denoised, CFG combine) -> sampler
 update.  W warm-up steps, then EXACTLY K steps timed between barrier + torch.cuda.synchronize(); max over ranks; `value` = (N * K) / T =
-batch-steps per second over the job (weak scaling: the per-GPU batch is fixed).  ms/image (nominal steps + VAE decode) is reported alongside.
+batch-steps per second over the job (weak scaling: the per-GPU batch is fixed); `ms_per_step` = T / K.
 
-Extra objects on the JSON line:
+A plain run does only what that figure needs: build the workload, prime (3 sampler steps: arena sizing, caches, HIP-graph capture), W warm-up
+steps, the K timed steps, the outputs (--dump-outputs) and the JSON line.  --dump-outputs DIR writes what the timed sampler run returned -- the
+denoised latents after its last step, gathered over ranks in global batch order -- as DIR/latents.npy (float32; an output above 64 MB would be
+replaced by a fixed seeded sample of its elements).  Weights, conditioning and noise are seeded, so the same arguments give the same inputs
+on every run and two builds can be compared output for output.
+
+--full adds everything else after the timed region: the VAE decode (ms/image = nominal steps + VAE decode) and the objects below, the clock
+sampler during the timed steps, and the baseline / other-configuration legs.  --breakdown and --vae-breakdown need --full.
+
+Extra objects on the --full JSON line:
   roofline      dominant kernel (MFMA implicit-GEMM conv/linear, 88 % of the step's FLOPs): algorithmic FLOP of all its launches in one
                 network forward / their summed HIP-event time (events recorded on the launch stream), vs the 2.5 PFLOP/s dense fp16/bf16
                 MFMA peak.  `roofline_attention` carries the same for the fused attention kernel, `roofline_groupnorm` the HBM-side one for
@@ -36,6 +45,7 @@ Test hook (tests/test_bench_launcher.py): `--stub-engine` replaces the workload 
 rank accounting and JSON contract can be exercised at world_size 2 without a GPU; its line says `"data": "stub"` and is not a measurement.
 """
 import argparse
+import contextlib
 import json
 import os
 import socket
@@ -97,15 +107,47 @@ def parse(argv=None):
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-vae", action="store_true")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--breakdown", default="", help="write the per-shape kernel-time table of one network forward to this file")
-    ap.add_argument("--vae-breakdown", default="", help="write the per-shape kernel-time table of one VAE decode to this file")
+    ap.add_argument("--breakdown", default="", help="(--full) write the per-shape kernel-time table of one network forward to this file")
+    ap.add_argument("--vae-breakdown", default="", help="(--full) write the per-shape kernel-time table of one VAE decode to this file")
     ap.add_argument("--rccl-selfcheck", action="store_true", help="(child process of the 1-GPU run) RCCL at world size 1: init, all-reduce, the job's broadcast + gathers on the device")
-    ap.add_argument("--no-rccl-selfcheck", action="store_true", help="1-GPU run: skip the RCCL world-1 leg")
+    ap.add_argument("--no-rccl-selfcheck", action="store_true", help="--full 1-GPU run: skip the RCCL world-1 leg")
     ap.add_argument("--torch-rocm-baseline", action="store_true", help="(child process of the 1-GPU run) the reference's op stack -- stock PyTorch-ROCm fp16 -- on the same workload and GPU")
-    ap.add_argument("--no-torch-rocm-baseline", action="store_true", help="1-GPU run: skip the PyTorch-ROCm leg")
-    ap.add_argument("--no-other-configs", action="store_true", help="default 1-GPU run: skip the two small-batch legs (BASELINE config 2 and SDXL batch 1) run after the timed region")
+    ap.add_argument("--no-torch-rocm-baseline", action="store_true", help="--full 1-GPU run: skip the PyTorch-ROCm leg")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full default 1-GPU run: skip the small-batch and Flux legs (BASELINE config 2, SDXL batch 1, Flux batch 2) run after the timed region")
     ap.add_argument("--stub-engine", action="store_true", help="launcher self-test without a GPU (gloo, no kernels); not a measurement")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the timed path returned in its last step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also run the VAE decode, roofline, clock sampling, CPU / PyTorch-ROCm baselines, RCCL "
+                                                        "self-check and other-configuration legs after the timed region")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    if a.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    if (a.breakdown or a.vae_breakdown) and not a.full:
+        ap.error("--breakdown / --vae-breakdown need --full")
+    return a
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, seed=0):
+    """Write each output as DIR/<name>.npy: float64 stays float64, everything else becomes float32.  If the outputs together exceed 64 MB, each is
+    replaced by a fixed seeded sample of its flattened elements (sorted indices), in proportion to its size."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = (t.double() if t.dtype == torch.float64 else t.float()).numpy()
+    total = sum(x.nbytes for x in host.values())
+    for name, x in host.items():
+        if total > DUMP_LIMIT_BYTES:
+            k = max(1, int(x.size * DUMP_LIMIT_BYTES // total))
+            idx = np.sort(np.random.default_rng(seed).choice(x.size, size=k, replace=False))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), x)
 
 
 def _free_port():
@@ -322,19 +364,21 @@ def stub_main(a, rank, world):
         dist.all_reduce(seen)
 
     def step():
-        return float((torch.ones(64, 64) @ torch.ones(64, 64)).sum())
+        return torch.ones(64, 64) @ torch.ones(64, 64)
     for _ in range(a.warmup):
         step()
     if world > 1:
         dist.barrier()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        step()
+        out = step()
     if world > 1:
         dist.barrier()
     el = torch.tensor([time.perf_counter() - t0])
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"stub": out})
     if rank == 0:
         print(json.dumps({"metric": "sampler it/s (UNet steps/sec)", "value": round(world * a.steps / float(el), 3), "unit": "it/s", "n_gpus": world,
                           "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(float(el) / a.steps * 1e3, 4), "higher_is_better": True,
@@ -503,7 +547,7 @@ def other_configs_leg(timeout=90):
         t0 = time.time()
         try:
             steps = "5" if "flux" in name else "10"
-            res = subprocess.run([sys.executable, os.path.abspath(__file__), *flags, "--steps", steps, "--warmup", "2", "--no-cpu-baseline", "--no-vae",
+            res = subprocess.run([sys.executable, os.path.abspath(__file__), *flags, "--steps", steps, "--warmup", "2", "--full", "--no-cpu-baseline", "--no-vae",
                                   "--no-rccl-selfcheck", "--no-other-configs", "--no-torch-rocm-baseline"], capture_output=True, text=True, timeout=2 * timeout if "flux" in name else timeout, env=env)
             line = next((ln for ln in reversed(res.stdout.splitlines()) if ln.startswith("{")), None)
             if line is None:
@@ -541,6 +585,8 @@ def main():
         raise SystemExit(f"bench.py: --gpus {a.gpus} but the launcher started WORLD_SIZE={world} ranks; refusing to report a number for the wrong N")
     if a.stub_engine:
         return stub_main(a, rank, world)
+    if not a.full:
+        a.no_vae = True   # the VAE decode is timed outside the sampler steps: a --full leg, so a plain run neither builds nor runs it
 
     import torch
     import forge_amd  # noqa: F401
@@ -658,8 +704,8 @@ def main():
         torch.cuda.synchronize()
         barrier()
         torch.cuda.synchronize()
-        clocks = ClockSampler(local)
-        with clocks:
+        clocks = ClockSampler(local) if a.full else None
+        with clocks or contextlib.nullcontext():
             t0 = time.perf_counter()
             lat = run_sampler(a.steps)           # exactly K timed steps
             torch.cuda.synchronize()
@@ -671,7 +717,16 @@ def main():
             torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
             elapsed = float(tmax.item())
 
-        # ---- VAE decode (per-job, outside the step loop) and latent gather -------------------------------------
+        # ---- latent gather (what the job returns) and the outputs of the timed run ------------------------------------
+        t0 = time.perf_counter()
+        gathered = fdist.gather_latents(lat, total)
+        torch.cuda.synchronize()
+        t_gather = time.perf_counter() - t0
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, {"latents": gathered})   # what a caller of the timed sampler run receives: [global batch, C, H, W]
+        del gathered
+
+        # ---- VAE decode (per-job, outside the step loop; --full) ------------------------------------------------------------
         vae_ms = None
         if not a.no_vae:
             eng.decode_first_stage(lat)          # untimed: sizes the VAE arena for this batch
@@ -687,15 +742,10 @@ def main():
                     torch.cuda.synchronize()
                     vprof.summary()
                 write_breakdown(a.vae_breakdown, vprof)
-        t0 = time.perf_counter()
-        gathered = fdist.gather_latents(lat, total)
-        torch.cuda.synchronize()
-        t_gather = time.perf_counter() - t0
-        del gathered
 
         # ---- roofline of the dominant kernels: HIP events around every launch in one eager network forward ----------
         roof = attn_roof = xattn_roof = gn_roof = None
-        if rank == 0 and not a.no_roofline:
+        if rank == 0 and a.full and not a.no_roofline:
             if is_flux:
                 net = km.diffusion_model
                 x = torch.randn(bpg, 16, latent, latent, device=dev)
@@ -775,15 +825,16 @@ def main():
         "step_tflops_per_gpu": None if fl is None else round(fl / 1e12, 2),
         "achieved_tflops_per_gpu": None if fl is None else round(fl / (ms_per_step * 1e-3) / 1e12, 1),
         "step_frac_of_mfma_peak": None if fl is None else round(fl / (ms_per_step * 1e-3) / MFMA_PEAK, 4),
-        "vae_decode_ms_per_batch": None if vae_ms is None else round(vae_ms, 1),
-        f"ms_per_image_{nominal}_steps_plus_vae": None if vae_ms is None else round((nominal * ms_per_step + vae_ms) / bpg, 1),
         "comm_ms": {"broadcast_cond": round(t_bcast * 1e3, 2), "gather_latents": round(t_gather * 1e3, 2)},
         "build_s": round(t_build, 1),
-        "clocks_during_timed_steps": clocks.summary(),
         "kernel_source_hash": kernel_source_hash(),          # of the loaded binary (fmx_build_info)
         "source_tree_hash": source_tree_hash(),              # of csrc/ on disk: differs from the line above when the .so is stale
         "knobs": {"active": _knobs(False), "set_but_ignored": _knobs(True)},   # development A/B knobs (need FMX_ALLOW_KNOBS=1); {} = the default kernels
     }
+    if a.full:
+        out["vae_decode_ms_per_batch"] = None if vae_ms is None else round(vae_ms, 1)
+        out[f"ms_per_image_{nominal}_steps_plus_vae"] = None if vae_ms is None else round((nominal * ms_per_step + vae_ms) / bpg, 1)
+        out["clocks_during_timed_steps"] = clocks.summary()
     if roof:
         out["roofline"] = roof
     if attn_roof:
@@ -792,7 +843,7 @@ def main():
         out["roofline_attention_short_keys"] = xattn_roof
     if gn_roof:
         out["roofline_groupnorm"] = gn_roof
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         try:
             dt, nthreads, note = cpu_baseline(model, ucfg, latent, sampler_name, cfg_scale)
             out["cpu_baseline"] = {"value": round(1.0 / (fwd_per_image * bpg * dt), 6), "unit": "it/s", "cores": nthreads, "kind": "port",
@@ -803,7 +854,7 @@ def main():
         except Exception as e:  # the baseline must never take the bench line down
             out["cpu_baseline"] = {"value": None, "error": repr(e)}
     default_workload = a.config == "sdxl-b8-euler20" and not (a.model or a.res or a.batch or a.sampler)
-    if rank == 0 and world == 1 and not a.no_torch_rocm_baseline and default_workload:
+    if rank == 0 and world == 1 and a.full and not a.no_torch_rocm_baseline and default_workload:
         # the reference's own op stack on THIS GPU, same network step (child process, after the timed region).  `vs_baseline` = native / that: context --
         # BASELINE.md publishes no number for this metric, and the target is the kernel roofline, not this ratio
         tb = torch_rocm_baseline_leg()
@@ -812,9 +863,9 @@ def main():
         if tb.get("ok") and tb.get("it_per_s_equivalent"):
             out["vs_baseline"] = round(value / tb["it_per_s_equivalent"], 3)
             out["vs_baseline_note"] = "native it/s / same-GPU PyTorch-ROCm it/s-equivalent (torch_rocm_baseline); context only -- BASELINE.md holds no published number for this metric"
-    if rank == 0 and world == 1 and not a.no_rccl_selfcheck:
+    if rank == 0 and world == 1 and a.full and not a.no_rccl_selfcheck:
         out["rccl_world1"] = rccl_world1_leg()     # after the timed region, in a child process
-    if rank == 0 and world == 1 and not a.no_other_configs and a.config == "sdxl-b8-euler20" and not (a.model or a.res or a.batch or a.sampler):
+    if rank == 0 and world == 1 and a.full and not a.no_other_configs and a.config == "sdxl-b8-euler20" and not (a.model or a.res or a.batch or a.sampler):
         out["other_configs"] = other_configs_leg()  # after the timed region, child processes
     if rank == 0:
         print(json.dumps(out), flush=True)

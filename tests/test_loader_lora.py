@@ -1,7 +1,10 @@
 """CPU: checkpoint splitting / model-family detection / LoRA key maps and patch parsing of forge_amd.backend.{loader,patcher.lora}
-against fixtures produced by the REAL reference (oracle/make_golden.py gen_lora) and, when /root/reference is present, against
-the reference's own functions."""
+against fixtures produced by the REAL reference (oracle/make_golden.py gen_lora), against what the reference's own functions returned
+(tests/golden/ref_lora_key_maps.json.gz) and against the configuration files it ships (tests/golden/hf_configs/; both by oracle/make_ref_fixtures.py)."""
+import gzip
 import hashlib
+import json
+import os
 
 import pytest
 import torch
@@ -12,9 +15,14 @@ from forge_amd.backend import loader
 from forge_amd.backend.misc.diffusers_state_dict import unet_to_diffusers
 from forge_amd.backend.nn.layout import unet_param_shapes, vae_decoder_param_shapes, vae_encoder_param_shapes
 from forge_amd.backend.patcher import lora as nlora
-from oracle import ref_import
+from conftest import GOLDEN, load_golden
 
-from conftest import load_golden
+HF_CONFIGS = os.path.join(GOLDEN, "hf_configs")   # backend/huggingface/ of the reference: the files the detection tests read
+
+
+def _ref_key_maps():
+    with gzip.open(os.path.join(GOLDEN, "ref_lora_key_maps.json.gz"), "rt") as f:
+        return json.load(f)
 
 
 def _meta_sd(shapes, prefix=""):
@@ -92,19 +100,13 @@ def test_lora_key_map_matches_reference_fixture():
     assert hashlib.sha256(txt.encode()).hexdigest() == g["key_map_sha256"]
 
 
-@pytest.mark.skipif(not ref_import.reference_available(), reason="needs /root/reference")
 @pytest.mark.parametrize("cfg", [synth.SD15_UNET_CONFIG, synth.SDXL_UNET_CONFIG, synth.TINY_SDXL_UNET_CONFIG])
 def test_lora_key_map_and_diffusers_names_vs_reference(cfg):
-    import importlib
-    from types import SimpleNamespace
-    ref_import.load_reference()
-    rl = importlib.import_module("backend.patcher.lora")
-    cu = importlib.import_module("packages_3rdparty.comfyui_lora_collection.utils")
-    rcfg = {k: (list(v) if isinstance(v, (list, tuple)) else v) for k, v in cfg.items()}
-    assert cu.unet_to_diffusers(dict(rcfg)) == unet_to_diffusers(cfg)
-    keys = {"diffusion_model." + k: None for k in unet_param_shapes(cfg)}
-    model = SimpleNamespace(state_dict=lambda: keys, diffusion_model=SimpleNamespace(config=rcfg), config=SimpleNamespace(huggingface_repo="sd"))
-    assert rl.model_lora_keys_unet(model, {}) == _key_map(cfg)
+    """unet_to_diffusers and the LoRA key map against the reference's unet_to_diffusers / model_lora_keys_unet on the same configuration."""
+    name = {id(synth.SD15_UNET_CONFIG): "sd15", id(synth.SDXL_UNET_CONFIG): "sdxl", id(synth.TINY_SDXL_UNET_CONFIG): "tiny_sdxl"}[id(cfg)]
+    ref = _ref_key_maps()["unet"][name]
+    assert ref["unet_to_diffusers"] == unet_to_diffusers(cfg)
+    assert ref["model_lora_keys_unet"] == _key_map(cfg)
 
 
 def test_load_lora_patch_parsing():
@@ -227,14 +229,13 @@ def test_flux_checkpoint_detection_and_split():
         loader.split_flux_state_dict({k: v.to(torch.float8_e4m3fn) for k, v in tr.items()})
 
 
-@pytest.mark.skipif(not ref_import.reference_available(), reason="needs /root/reference")
 def test_flux_and_vae_detection_agree_with_the_configuration_files_the_reference_ships():
     """The reference builds Flux from backend/huggingface/black-forest-labs/FLUX.1-{dev,schnell}/{transformer,vae}/config.json (diffusers field
     names); what the loader reads off a full-size state dict must describe the same networks."""
     import json
     import os
     from forge_amd.backend.nn.layout import flux_param_shapes
-    root = os.path.join(ref_import.REFERENCE_ROOT, "backend", "huggingface", "black-forest-labs")
+    root = os.path.join(HF_CONFIGS, "black-forest-labs")
     for repo, guidance in (("FLUX.1-dev", True), ("FLUX.1-schnell", False)):
         want = json.load(open(os.path.join(root, repo, "transformer", "config.json")))
         cfg = dict(synth.FLUX_DEV_CONFIG, guidance_embed=guidance)
@@ -253,7 +254,6 @@ def test_flux_and_vae_detection_agree_with_the_configuration_files_the_reference
             assert (tuple(vgot[k]) if k == "block_out_channels" else vgot[k]) == (tuple(vwant[k]) if k == "block_out_channels" else vwant[k]), k
 
 
-@pytest.mark.skipif(not ref_import.reference_available(), reason="needs /root/reference")
 @pytest.mark.parametrize("repo,base,override", [
     ("runwayml/stable-diffusion-v1-5", "SD15_UNET_CONFIG", {}),
     ("runwayml/stable-diffusion-inpainting", "SD15_UNET_CONFIG", {"in_channels": 9}),
@@ -264,7 +264,7 @@ def test_unet_detection_agrees_with_the_configuration_files_the_reference_ships(
     level, ResBlocks per level, transformer depth per level, heads, context / label widths, linear vs conv projections)."""
     import json
     import os
-    want = json.load(open(os.path.join(ref_import.REFERENCE_ROOT, "backend", "huggingface", repo, "unet", "config.json")))
+    want = json.load(open(os.path.join(HF_CONFIGS, repo, "unet", "config.json")))
     cfg = dict(getattr(synth, base), **override)
     got = loader.detect_unet_config(_meta_sd(unet_param_shapes(cfg), loader.UNET_PREFIX))
     mc = got["model_channels"]
@@ -306,14 +306,13 @@ def _ldm_config_from_diffusers(want):
     return cfg
 
 
-@pytest.mark.skipif(not ref_import.reference_available(), reason="needs /root/reference")
 @pytest.mark.parametrize("repo", ["stabilityai/stable-diffusion-2-1", "stabilityai/stable-diffusion-xl-refiner-1.0", "stabilityai/stable-diffusion-xl-base-1.0"])
 def test_unet_detection_round_trips_the_sd2_and_refiner_structures(repo):
     """SD2.1 (context 1024, linear projections, 64 channels per head, last level without attention) and the SDXL refiner (384-wide, four levels,
     attention only in the two middle ones, 2560-wide label input): shipped config -> LDM arguments -> parameter shapes -> detection."""
     import json
     import os
-    want = json.load(open(os.path.join(ref_import.REFERENCE_ROOT, "backend", "huggingface", repo, "unet", "config.json")))
+    want = json.load(open(os.path.join(HF_CONFIGS, repo, "unet", "config.json")))
     cfg = _ldm_config_from_diffusers(want)
     got = loader.detect_unet_config(_meta_sd(unet_param_shapes(cfg), loader.UNET_PREFIX))
     for k, v in cfg.items():
@@ -323,7 +322,6 @@ def test_unet_detection_round_trips_the_sd2_and_refiner_structures(repo):
         assert {k: got[k] for k in synth.SDXL_UNET_CONFIG} == synth.SDXL_UNET_CONFIG
 
 
-@pytest.mark.skipif(not ref_import.reference_available(), reason="needs /root/reference")
 def test_family_constants_match_the_shipped_scheduler_and_vae_configs():
     """The constants no tensor carries -- noise schedule, VAE scaling / shift factors, the Flux time-shift parameters -- against the scheduler and
     VAE configuration files under backend/huggingface/."""
@@ -331,7 +329,7 @@ def test_family_constants_match_the_shipped_scheduler_and_vae_configs():
     import json
     import os
     from forge_amd.backend.modules.k_prediction import PredictionFlux
-    hub = os.path.join(ref_import.REFERENCE_ROOT, "backend", "huggingface")
+    hub = HF_CONFIGS
     load = lambda *p: json.load(open(os.path.join(hub, *p)))  # noqa: E731
     for repo in ("runwayml/stable-diffusion-v1-5", "stabilityai/stable-diffusion-xl-base-1.0"):
         sch = load(repo, "scheduler", "scheduler_config.json")
@@ -369,22 +367,20 @@ def test_flux_lora_key_map_matches_reference_fixture():
     assert touched == set(g["merged"])
 
 
-@pytest.mark.skipif(not ref_import.reference_available(), reason="needs /root/reference")
 def test_flux_to_diffusers_vs_reference():
-    import importlib
+    """flux_to_diffusers against the reference's (function targets compared through their output on the fixture's test input)."""
     from forge_amd.backend.misc.diffusers_state_dict import flux_to_diffusers
-    ref_import.load_reference()
-    cu = importlib.import_module("packages_3rdparty.comfyui_lora_collection.utils")
-    for cfg in (synth.TINY_FLUX_CONFIG, synth.FLUX_DEV_CONFIG):
-        ours, theirs = flux_to_diffusers(cfg, output_prefix="diffusion_model."), cu.flux_to_diffusers(dict(cfg), output_prefix="diffusion_model.")
+    from oracle.make_ref_fixtures import TEST_INPUT, flux_target_record
+    ref = _ref_key_maps()["flux_to_diffusers"]
+    for name, cfg in (("tiny_flux", synth.TINY_FLUX_CONFIG), ("flux_dev", synth.FLUX_DEV_CONFIG)):
+        ours, theirs = flux_to_diffusers(cfg, output_prefix="diffusion_model."), ref[name]
         assert set(ours) == set(theirs)
         for k in ours:
             a, b = ours[k], theirs[k]
-            if isinstance(b, tuple) and len(b) > 2:
-                t = torch.arange(12.0).reshape(6, 2)
-                assert a[0] == b[0] and a[1] is None and torch.equal(a[2](t), b[2](t))
+            if isinstance(b, list) and len(b) > 2:
+                assert a[0] == b[0] and a[1] is None and torch.equal(a[2](TEST_INPUT), torch.tensor(b[2], dtype=TEST_INPUT.dtype))
             else:
-                assert a == b, k
+                assert flux_target_record(a) == b, k
 
 
 def test_bias_diff_on_a_slice_target_is_reported_not_raised():

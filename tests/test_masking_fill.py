@@ -1,5 +1,6 @@
-"""`forge_amd.modules.masking.fill` against the reference's modules/masking.py:80-95 (imported by path when /root/reference is present) and against a
-committed fixture generated from it (tests/golden/masking_fill.pt, made by this file: `python tests/test_masking_fill.py`)."""
+"""`forge_amd.modules.masking.fill` against the reference's modules/masking.py:80-95 through committed fixtures generated from it:
+tests/golden/masking_fill.pt (the tensor path, made by this file: `python tests/test_masking_fill.py`) and tests/golden/ref_masking_fill.pt
+(the PIL path, made by oracle/make_ref_fixtures.py)."""
 import importlib.util
 import os
 import sys
@@ -12,9 +13,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 import forge_amd  # noqa: E402,F401
 from forge_amd.modules import masking  # noqa: E402
+from oracle import ref_import  # noqa: E402
 
-REF = "/root/reference/modules/masking.py"
+REF = os.path.join(ref_import.REFERENCE_ROOT, "modules", "masking.py")   # read only by the fixture recipe below
 FIX = os.path.join(HERE, "golden", "masking_fill.pt")
+FIX_PIL = os.path.join(HERE, "golden", "ref_masking_fill.pt")
 
 
 def _case():
@@ -39,13 +42,13 @@ def _pil(img, mask):
     return Image.fromarray(a, "RGB"), Image.fromarray(m, "L")
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="needs /root/reference")
 def test_fill_equals_the_reference_function():
     img, mask = _case()
-    ref_fill = _ref_fill()
+    want = torch.load(FIX_PIL)["filled_pil_u8"]
+    assert want.shape[0] == img.shape[0]
     for i in range(img.shape[0]):
         pi, pm = _pil(img[i], mask)
-        assert np.array_equal(np.array(masking.fill(pi, pm)), np.array(ref_fill(pi, pm)))
+        assert np.array_equal(np.array(masking.fill(pi, pm)), want[i].numpy())
 
 
 def test_fill_tensor_matches_the_reference_fixture():

@@ -80,26 +80,28 @@ def test_prompt_editing_schedules_match_the_reference_doctests():
     assert g("\\\\[not:3\\\\] (x:1.2)") == [[10, "\\\\[not:3\\\\] (x:1.2)"]]
 
 
-def test_parse_prompt_attention_randomised_against_the_reference_module():
-    """4 000 random strings over the syntax's alphabet through both parsers (the reference's parsing.py needs nothing but `re`).  Runs where
-    /root/reference exists (the authoring container); the committed fixture above covers the GPU box."""
-    import importlib.util
-    import os
+def random_prompts(n=4000, seed=0):
+    """n random strings over the syntax's alphabet (the inputs of ref_prompt_attention_random.json.gz, oracle/make_ref_fixtures.py)."""
     import random
-    import pytest
-    path = "/root/reference/backend/text_processing/parsing.py"
-    if not os.path.exists(path):
-        pytest.skip("reference not present")
-    spec = importlib.util.spec_from_file_location("_ref_parsing", path)
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    rnd = random.Random(0)
+    rnd = random.Random(seed)
     alphabet = ["a", "cat ", "(", ")", "[", "]", ":", "1.2", " ", "\\(", "\\)", "\\\\", "\\", " BREAK ", "BREAK", ",", ":0.5)", ": 1.3 )", "dog", "(((", "]]",
                 ":-1)", ":.5)", "\n", "x:y"]
-    for _ in range(4000):
-        s = "".join(rnd.choice(alphabet) for _ in range(rnd.randint(1, 12)))
-        for mode in ("Original", "None"):
-            assert parse_prompt_attention(s, mode) == ref.parse_prompt_attention(s, mode), repr(s)
+    return ["".join(rnd.choice(alphabet) for _ in range(rnd.randint(1, 12))) for _ in range(n)]
+
+
+def test_parse_prompt_attention_randomised_against_the_reference_module():
+    """4 000 random strings over the syntax's alphabet through the native parser, against what the reference's parsing.py returned for each of
+    them in both modes (tests/golden/ref_prompt_attention_random.json.gz, recorded by oracle/make_ref_fixtures.py)."""
+    import gzip
+    import json
+    import os
+    from conftest import GOLDEN
+    with gzip.open(os.path.join(GOLDEN, "ref_prompt_attention_random.json.gz"), "rt") as f:
+        rows = json.load(f)
+    prompts = random_prompts()
+    assert [s for s, mode, _ in rows] == [s for s in prompts for _ in ("Original", "None")]
+    for s, mode, want in rows:
+        assert parse_prompt_attention(s, mode) == want, repr(s)
 
 
 def test_prompt_schedule_invariants():

@@ -14,12 +14,12 @@ for w in "$@"; do
     sharp) FMX_PARITY_LOG=$O/sharp_parity.jsonl timeout 1500 python -m pytest tests/test_gpu_sharp_parity.py -m gpu -q -s --tb=short --durations=10 2>&1 | grep -v "^\[parity\]" | tail -40 > $O/sharp.log; tail -25 $O/sharp.log | cut -c1-1200;;
     tests) FMX_PARITY_LOG=$O/parity.jsonl timeout 1700 python -m pytest tests -m gpu -q -s --tb=line --durations=25 2>&1 | grep -v "^\[parity\]" | tail -150 > $O/pytest_gpu.log; tail -40 $O/pytest_gpu.log | cut -c1-400;;
     smoke) timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -3 $O/smoke.log;;
-    bench) timeout 1500 python bench.py --breakdown $O/breakdown.jsonl --vae-breakdown $O/vae_breakdown.jsonl > $O/bench.json 2> $O/bench.err; cat $O/bench.json; tail -3 $O/bench.err;;
+    bench) timeout 1500 python bench.py --full --breakdown $O/breakdown.jsonl --vae-breakdown $O/vae_breakdown.jsonl > $O/bench.json 2> $O/bench.err; cat $O/bench.json; tail -3 $O/bench.err;;
     torchbase) timeout 600 python bench.py --torch-rocm-baseline > $O/torchbase.log 2>&1; tail -5 $O/torchbase.log | cut -c1-600;;
-    benchflux) timeout 900 python bench.py --config flux-b2-bf16 --steps 5 --warmup 2 --no-cpu-baseline --no-rccl-selfcheck --breakdown $O/breakdown_flux.jsonl > $O/bench_flux.json 2> $O/bench_flux.err; cat $O/bench_flux.json | cut -c1-1800; tail -2 $O/bench_flux.err; head -12 $O/breakdown_flux.jsonl;;
-    vaebench) timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-rccl-selfcheck --no-other-configs --no-torch-rocm-baseline --no-roofline --vae-breakdown $O/vae_breakdown.jsonl 2>> $O/vaebench.err | benchline vae >> $O/vaebench.jsonl; cat $O/vaebench.jsonl; head -30 $O/vae_breakdown.jsonl;;
-    ab_env) for E in $ABENV0 $ABENV1 $ABENV0 $ABENV1; do env ${E//,/ } timeout 600 python bench.py ${ABFLAGS:---no-vae} --no-cpu-baseline --no-rccl-selfcheck --no-other-configs --no-torch-rocm-baseline --steps 10 2>> $O/ab.err | benchline "$E" >> $O/ab.jsonl; done; cat $O/ab.jsonl; tail -3 $O/ab.err;;
-    ab_lib) for L in "" $ABLIB "" $ABLIB; do FMX_LIB=$L timeout 600 python bench.py ${ABFLAGS:---no-vae} --no-cpu-baseline --no-rccl-selfcheck --no-other-configs --no-torch-rocm-baseline --steps 10 2>> $O/ab.err | benchline "lib=$L" >> $O/ab.jsonl; done; cat $O/ab.jsonl; tail -3 $O/ab.err;;
+    benchflux) timeout 900 python bench.py --full --config flux-b2-bf16 --steps 5 --warmup 2 --no-cpu-baseline --no-rccl-selfcheck --breakdown $O/breakdown_flux.jsonl > $O/bench_flux.json 2> $O/bench_flux.err; cat $O/bench_flux.json | cut -c1-1800; tail -2 $O/bench_flux.err; head -12 $O/breakdown_flux.jsonl;;
+    vaebench) timeout 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-rccl-selfcheck --no-other-configs --no-torch-rocm-baseline --no-roofline --vae-breakdown $O/vae_breakdown.jsonl 2>> $O/vaebench.err | benchline vae >> $O/vaebench.jsonl; cat $O/vaebench.jsonl; head -30 $O/vae_breakdown.jsonl;;
+    ab_env) for E in $ABENV0 $ABENV1 $ABENV0 $ABENV1; do env ${E//,/ } timeout 600 python bench.py --full ${ABFLAGS:---no-vae} --no-cpu-baseline --no-rccl-selfcheck --no-other-configs --no-torch-rocm-baseline --steps 10 2>> $O/ab.err | benchline "$E" >> $O/ab.jsonl; done; cat $O/ab.jsonl; tail -3 $O/ab.err;;
+    ab_lib) for L in "" $ABLIB "" $ABLIB; do FMX_LIB=$L timeout 600 python bench.py --full ${ABFLAGS:---no-vae} --no-cpu-baseline --no-rccl-selfcheck --no-other-configs --no-torch-rocm-baseline --steps 10 2>> $O/ab.err | benchline "lib=$L" >> $O/ab.jsonl; done; cat $O/ab.jsonl; tail -3 $O/ab.err;;
     kb) timeout 900 python tools/bench_kernels.py $KB > $O/kb_$KB.jsonl 2> $O/kb_$KB.err; cat $O/kb_$KB.jsonl | cut -c1-400; tail -3 $O/kb_$KB.err;;
     attnrot) FMX_ATTN_WS_ROT=1 timeout 900 python -m pytest tests/test_gpu_kernels.py tests/test_gpu_flux.py tests/test_gpu_flux_sharp_parity.py -m gpu -q --tb=short -k "d128 or attention or flux_forward_at_its_own_width or tiny or sharp or stage" 2>&1 | tail -15 > $O/attnrot_tests.log; tail -6 $O/attnrot_tests.log | cut -c1-300;
              for E in 0 1 0 1; do FMX_ATTN_WS_ROT=$E timeout 300 python tools/bench_kernels.py attn128 >> $O/attnrot.jsonl 2>> $O/attnrot.err; done; cat $O/attnrot.jsonl | cut -c1-300; tail -2 $O/attnrot.err;;
@@ -34,15 +34,15 @@ for w in "$@"; do
                find $O/$PMCTAG/pmc_$name -name '*kernel_trace.csv' -delete; done
              python tools/pmc_mfma_summary.py $O/$PMCTAG > $O/pmc_$PMCTAG.json; cat $O/pmc_$PMCTAG.json | head -60;;
     prof_flux) (cd /tmp && export TMPDIR=/tmp && timeout 1200 rocprofv3 --kernel-trace --stats -f csv -d $O/prof_flux -o kt -- \
-            python $R/bench.py --config flux-b2-bf16 --steps 5 --warmup 2 --no-cpu-baseline --no-rccl-selfcheck --no-roofline > $O/prof_flux_bench.log 2>&1); tail -1 $O/prof_flux_bench.log | cut -c1-300;
+            python $R/bench.py --full --config flux-b2-bf16 --steps 5 --warmup 2 --no-cpu-baseline --no-rccl-selfcheck --no-roofline > $O/prof_flux_bench.log 2>&1); tail -1 $O/prof_flux_bench.log | cut -c1-300;
           find $O/prof_flux -name '*kernel_trace.csv' -delete; head -25 $O/prof_flux/kt_kernel_stats.csv | cut -c1-220;;
     kbvar) for L in "" $KBLIBS; do FMX_LIB=$L timeout 600 python tools/bench_kernels.py $KB >> $O/kbvar_$KB.jsonl 2>> $O/kbvar_$KB.err; done; cat $O/kbvar_$KB.jsonl | cut -c1-500; tail -3 $O/kbvar_$KB.err;;
     pyt) eval timeout 1200 python -m pytest $PYT -m gpu -q --tb=short -s 2>&1 | grep -v "^\[parity\]" | tail -40 > $O/pyt.log; tail -30 $O/pyt.log | cut -c1-600;;
     prof) (cd /tmp && export TMPDIR=/tmp && timeout 1200 rocprofv3 --kernel-trace --stats -f csv -d $O/prof -o kt -- \
-            python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs --no-torch-rocm-baseline --no-rccl-selfcheck > $O/prof_bench.log 2>&1); tail -2 $O/prof_bench.log | cut -c1-600;
+            python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs --no-torch-rocm-baseline --no-rccl-selfcheck > $O/prof_bench.log 2>&1); tail -2 $O/prof_bench.log | cut -c1-600;
           find $O/prof -name '*kernel_trace.csv' -size +20M -delete; ls -la $O/prof/* | head;;
     pmc_hbm) for C in FETCH_SIZE WRITE_SIZE; do (cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --kernel-trace --pmc $C -f csv -d $O/pmc_$C -o pmc -- \
-            python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-vae --no-roofline --no-graph --no-other-configs --no-torch-rocm-baseline --no-rccl-selfcheck > $O/pmc_$C.log 2>&1); tail -1 $O/pmc_$C.log | cut -c1-300; done;
+            python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-vae --no-roofline --no-graph --no-other-configs --no-torch-rocm-baseline --no-rccl-selfcheck > $O/pmc_$C.log 2>&1); tail -1 $O/pmc_$C.log | cut -c1-300; done;
           python $R/tools/pmc_summary.py $O > $O/pmc_summary.json; cat $O/pmc_summary.json | cut -c1-1500; find $O -name '*counter_collection.csv' -size +30M -delete; find $O -name '*kernel_trace.csv' -delete;;
   esac
 done
