@@ -54,7 +54,8 @@ __global__ void add_control_nchw_kernel(f16* __restrict__ h, const float* __rest
 __global__ void act_kernel(const f16* __restrict__ x, f16* __restrict__ y, long n, int kind) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const float v = (float)x[i];
-    y[i] = (f16)(kind == 0 ? v / (1.0f + __expf(-1.702f * v)) : kind == 1 ? gelu_erf_f(v) : fmaxf(v, 0.f));
+    // ReLU as `v > 0 ? v : 0` with NaN passed through (torch.relu propagates it; fmaxf would turn it into 0 and hide it from the guards)
+    y[i] = (f16)(kind == 0 ? v / (1.0f + __expf(-1.702f * v)) : kind == 1 ? gelu_erf_f(v) : (v > 0.f || v != v) ? v : 0.f);
   }
 }
 

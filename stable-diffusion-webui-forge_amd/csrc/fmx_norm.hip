@@ -97,6 +97,16 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const f16* __restrict__ x
   }
 }
 
+// The statistics are one-pass sums {sum x, sum x^2} in fp32 chunk partials; the FOLD of those partials into mean and variance runs in double
+// (both finalize sites below).  var = E[x^2] - E[x]^2 cancels mean^2 / std^2 of its leading bits, and an fp32 fold loses ~2^-24 * (mean / std)^2
+// of the variance: at mean / std = 100 (fp16 inputs) that alone was ~1.5 output ulps; folded in double, the error left is the rounding inside the
+// fp32 partials, which dominates only beyond mean / std ~ 200 (GroupNorm; tests/test_gpu_kernels_bf16.py offset sweep).
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
 // ---- finalize: fold the chunk partials of one (image, group) into per-channel (scale, shift) ---------------------------------------
 // grid (groups, n), one wave per block.  The channels of the (virtually concatenated) input come from up to two partial buffers with
 // their own chunk counts (the two producers may have tiled differently).  Item i of a group and source = (channel i / nch, chunk i % nch);
@@ -107,7 +117,7 @@ __global__ __launch_bounds__(64) void gn_finalize_kernel(const float* __restrict
   const int C = c0 + c1;
   const int cpg = C / groups;
   const int g = blockIdx.x, img = blockIdx.y, lane = threadIdx.x;
-  float s = 0.f, q = 0.f;
+  double s = 0.0, q = 0.0;
   // the group's (channel, chunk) records of each source, flattened over the lanes: all loads of a lane are independent (a loop over
   // channels with a few chunks each leaves most lanes idle behind one L2 round trip per channel)
   auto accumulate = [&](const float* base, int nch, int cs, int lo, int hi) {   // source-local channels [lo, hi)
@@ -123,11 +133,12 @@ __global__ __launch_bounds__(64) void gn_finalize_kernel(const float* __restrict
   const int g_lo = g * cpg, g_hi = g_lo + cpg;
   if (g_lo < c0) accumulate(p0, nch0, c0, g_lo, min(g_hi, c0));
   if (g_hi > c0) accumulate(p1, nch1, c1, max(g_lo, c0) - c0, g_hi - c0);
-  s = wave_sum(s);
-  q = wave_sum(q);
-  const float cnt = (float)cpg * (float)hw;
-  const float mean = s / cnt;
-  const float rstd = rsqrtf(fmaxf(q / cnt - mean * mean, 0.f) + eps);
+  s = wave_sum_d(s);
+  q = wave_sum_d(q);
+  const double cnt = (double)cpg * (double)hw;
+  const double mean_d = s / cnt;
+  const float mean = (float)mean_d;
+  const float rstd = rsqrtf((float)fmax(q / cnt - mean_d * mean_d, 0.0) + eps);
   for (int ci = lane; ci < cpg; ci += 64) {
     const int c = g * cpg + ci;
     const float sc = rstd * (float)gamma[c];
@@ -165,21 +176,21 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const f16* __restrict__ x
       const bool second = c >= c0;
       const int cl = second ? c - c0 : c, cs = second ? c1 : c0, nch = second ? fu.nch1 : fu.nch0;
       const float* b = (second ? fu.p1 : fu.p0) + ((long)img * nch * cs + cl) * 2;
-      float s = 0.f, q = 0.f;
+      double s = 0.0, q = 0.0;
       for (int ch = 0; ch < nch; ++ch) {
         const f32x2 v = *reinterpret_cast<const f32x2*>(b + (long)ch * cs * 2);
         s += v[0];
         q += v[1];
       }
-      scale[c] = s;
-      shift[c] = q;
+      scale[c] = (float)s;   // one rounding per channel sum (independent, half an ulp each), not a running fp32 sum
+      shift[c] = (float)q;
     }
     __syncthreads();
     // 2. per group (32 of them, 8 threads each): channels j, j + 8, ... of the group, then a fixed 8-lane butterfly
     const int cpg = C >> 5;
     {
       const int g = tid >> 3, j = tid & 7;
-      float s = 0.f, q = 0.f;
+      double s = 0.0, q = 0.0;
       for (int ci = j; ci < cpg; ci += 8) {
         s += scale[g * cpg + ci];
         q += shift[g * cpg + ci];
@@ -190,18 +201,19 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const f16* __restrict__ x
         q += __shfl_xor(q, d);
       }
       __syncthreads();   // every read of the per-channel sums is done before step 3 overwrites them
-      if (j == 0) {
-        ss[2 * C + g] = s;
-        ss[2 * C + 32 + g] = q;
+      if (j == 0) {   // group mean and rstd, folded in double (see wave_sum_d)
+        const double cnt = (double)cpg * (double)hw;
+        const double mean = s / cnt;
+        ss[2 * C + g] = (float)mean;
+        ss[2 * C + 32 + g] = rsqrtf((float)fmax(q / cnt - mean * mean, 0.0) + fu.eps);
       }
     }
     __syncthreads();
     // 3. per channel: scale = rstd gamma, shift = beta - mean rstd gamma
-    const float cnt = (float)cpg * (float)hw;
     for (int c = tid; c < C; c += 256) {
       const int g = c / cpg;
-      const float mean = ss[2 * C + g] / cnt;
-      const float rstd = rsqrtf(fmaxf(ss[2 * C + 32 + g] / cnt - mean * mean, 0.f) + fu.eps);
+      const float mean = ss[2 * C + g];
+      const float rstd = ss[2 * C + 32 + g];
       const float sc = rstd * (float)fu.gamma[c];
       scale[c] = sc;
       shift[c] = (float)fu.beta[c] - mean * sc;

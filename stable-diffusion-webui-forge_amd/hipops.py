@@ -575,13 +575,15 @@ def silu(x, out=None):
 def add_control_(h, ctrl, alpha=1.0):
     """h [B,H,W,C] fp16 NHWC += alpha * ctrl [B,C,H,W] (ControlNet residual, unet.py:44-52), in place.  A residual whose MEMORY is already
     channels-last (the native ControlNet hands out NCHW views of NHWC buffers) is added elementwise; an NCHW-contiguous one goes through
-    the transposing kernel."""
+    the transposing kernel, and so does a channels-last one whose storage (or h's) is not 16-byte aligned: the elementwise kernel reads and
+    writes 16-byte vectors (fmx_add_scaled_f16 refuses such pointers), the transposing one has no alignment requirement."""
     b, hh, ww, c = h.shape
     clear_stats(h)  # h changes in place: statistics its producer left are stale
     if tuple(ctrl.shape) != (b, c, hh, ww):
         raise ValueError(f"control residual {tuple(ctrl.shape)} does not match activation {(b, c, hh, ww)}")
     nhwc = ctrl.permute(0, 2, 3, 1)
-    if ctrl.device == h.device and nhwc.is_contiguous() and ctrl.dtype in (torch.float16, torch.float32) and not (c == 1 or hh * ww == 1):
+    aligned = h.data_ptr() % 16 == 0 and nhwc.data_ptr() % 16 == 0
+    if ctrl.device == h.device and nhwc.is_contiguous() and aligned and ctrl.dtype in (torch.float16, torch.float32) and not (c == 1 or hh * ww == 1):
         _lib.check(_lib.lib().fmx_add_scaled_f16(_p(h), _p(nhwc), 1 if ctrl.dtype == torch.float32 else 0, float(alpha), h.numel(), stream_ptr()),
                    "fmx_add_scaled_f16")
         return h

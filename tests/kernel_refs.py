@@ -1,0 +1,219 @@
+"""fp64 references and ulp tolerances shared by the kernel-level parity tests (tests/test_gpu_kernels_bf16.py, tests/test_gpu_small_kernels.py)
+and their CPU companion (tests/test_kernel_ref_teeth.py), which plants one plausible bug into each reference and checks that the GPU tests'
+tolerance would reject it.
+
+Discipline: every reference is the same operation in fp64 on the kernel's own rounded inputs (the fp16 / bf16 tensors it read, upcast).
+A tolerance is `ulps` units in the last place of the REFERENCE value in the output element type plus an absolute floor `atol`;
+`excess()` is the largest error in units of that tolerance: <= 1 passes, and a planted bug must reach >= 4.  Plain module (not a
+conftest.py): the test files import it by name."""
+import math
+
+import torch
+import torch.nn.functional as F
+
+# (explicit mantissa bits, smallest normal exponent) per element type: one ulp of 1.0 is 2^-mant
+_FMT = {torch.float16: (10, -14), torch.bfloat16: (7, -126), torch.float32: (23, -126)}
+EPS = {dt: 2.0 ** -m for dt, (m, _) in _FMT.items()}   # fp16 2^-10 per ulp at 1 (2^-11 relative rounding), bf16 2^-7 (2^-8 relative)
+
+
+def ulp(want, dtype):
+    """one ulp of the fp64 values `want` in `dtype` (subnormal spacing below the normal range)"""
+    mant, emin = _FMT[dtype]
+    e = torch.floor(torch.log2(want.double().abs().clamp_min(2.0 ** emin)))
+    return torch.exp2(e - mant)
+
+
+def excess(got, want, dtype, ulps, atol=0.0):
+    """max |got - want| / (ulps * ulp(want) + atol) over the finite reference values; non-finite reference entries must match exactly"""
+    got, want = got.double().cpu(), want.double().cpu()
+    fin = torch.isfinite(want)
+    if not bool(torch.equal(got[~fin].nan_to_num(nan=1.5e308), want[~fin].nan_to_num(nan=1.5e308))):
+        return math.inf
+    if not bool(fin.any()):
+        return 0.0
+    err = (got[fin] - want[fin]).abs() / (ulps * ulp(want[fin], dtype) + atol)
+    return float(err.nan_to_num(nan=math.inf).max())
+
+
+def assert_within(got, want, dtype, ulps, atol, what):
+    e = excess(got, want, dtype, ulps, atol)
+    assert e <= 1.0, f"{what}: error {e:.3g}x the tolerance ({ulps} ulp of {dtype} + {atol:.3g})"
+
+
+def rounded(x, dtype):
+    """x rounded to dtype and back to fp64: the values a kernel reading `dtype` sees"""
+    return x.to(dtype).double()
+
+
+# ---- tolerances (ulps of the output type, absolute floor); each with the arithmetic behind it -----------------------------------------
+# conv / GEMM: fp32 accumulation (relative ~1e-6 over K <= 2304) then one rounding to the output (0.5 ulp), plus the epilogue's
+# fp32 adds; outputs that cancel to ~0 sit on the floor: 1 output ulp at the O(1) scale of the summed terms.
+CONV_TOL = {torch.bfloat16: (1.0, EPS[torch.bfloat16]), torch.float16: (1.0, EPS[torch.float16])}
+# GroupNorm apply: per-channel scale / shift folded in fp32, one fmaf + optional SiLU in fp32, one rounding: 1 ulp; the floor is one ulp at
+# 1.0 for outputs near zero whose error comes from the (fp32) mean, not from their own rounding.
+GN_TOL = {torch.bfloat16: (1.0, EPS[torch.bfloat16]), torch.float16: (1.0, EPS[torch.float16])}
+# attention: P is rounded to the element type before the P V MFMA (one rounding of weights <= 1, relative), O rounded once: 2 ulps of O,
+# floor 2 ulps at the O(1) value scale for outputs that average to ~0.
+ATTN_TOL = {torch.bfloat16: (2.0, 2 * EPS[torch.bfloat16]), torch.float16: (2.0, 2 * EPS[torch.float16])}
+# softmax rows: fp32 max / exp / sum, one rounding of each probability: 1 ulp; floor = 1 ulp at the smallest normal (underflowing tails)
+SOFTMAX_TOL = {torch.bfloat16: (1.0, 2.0 ** -133), torch.float16: (1.0, 2.0 ** -24)}
+# elementwise fp32 math (expf / erff / sinf, ~2 fp32 ulp) then one rounding to a 16-bit type: 1 ulp, floor = the smallest subnormal
+# step (fp16 2^-24) so that results in the subnormal range still have to be right
+ELEM_TOL = {torch.bfloat16: (1.0, 2.0 ** -133), torch.float16: (1.0, 2.0 ** -24)}
+# timestep embedding: cos / sin of arguments up to 1e6 (t * 1000 * guidance), argument a = t * freq rounded in fp32 first: the fp32 rounding
+# of `a` (|a| * 2^-24) is a phase error that the reference reproduces by evaluating on the same fp32 argument; 1 output ulp + floor of 1 ulp
+# at 1.0 (values near a zero crossing)
+TEMB_TOL = {torch.bfloat16: (1.0, EPS[torch.bfloat16]), torch.float16: (1.0, EPS[torch.float16])}
+# fp32-output boundary kernels (unpack image, sample posterior): fp32 arithmetic on 16-bit inputs, __expf (a few fp32 ulp): 8 fp32 ulps,
+# floor 2^-20 for outputs that cancel (mean + std * noise ~ 0)
+F32_TOL = (8.0, 2.0 ** -20)
+
+
+# ---- references -------------------------------------------------------------------------------------------------------------------
+def conv_ref(x, wt, bias=None, *, stride=1, pad=1, pad_rb=None, up=None, rowvec=None, residual=None):
+    """x NHWC, wt [co, ci, kh, kw] -> NHWC fp64.  pad_rb = (right, bottom) zero columns / rows only (VAE Downsample: F.pad(x, (0, 1, 0, 1))
+    then stride 2, pad 0); up = (UH, UW) nearest resize before the conv."""
+    xin = x.double().permute(0, 3, 1, 2)
+    if up is not None:
+        xin = F.interpolate(xin, size=list(up), mode="nearest")
+    if pad_rb is not None:
+        xin = F.pad(xin, (0, pad_rb[0], 0, pad_rb[1]))
+        pad = 0
+    y = F.conv2d(xin, wt.double(), None if bias is None else bias.double(), stride=stride, padding=pad)
+    if rowvec is not None:
+        y = y + rowvec.double()[:, :, None, None]
+    y = y.permute(0, 2, 3, 1)
+    if residual is not None:
+        y = y + residual.double().reshape(y.shape)
+    return y
+
+
+def groupnorm_ref(x, gamma, beta, eps, groups=32, silu=False):
+    """x NHWC (fp64 view of the rounded input) -> NHWC fp64"""
+    y = F.group_norm(x.double().permute(0, 3, 1, 2), groups, gamma.double(), beta.double(), eps).permute(0, 2, 3, 1)
+    return y * torch.sigmoid(y) if silu else y
+
+
+def stat_sums_ref(out, n):
+    """fp64 {sum, sum of squares} per (image, channel) of the stored output [n * hw, c] -> [n, c, 2]"""
+    o = out.double().reshape(n, -1, out.shape[-1])
+    return torch.stack([o.sum(1), (o * o).sum(1)], -1)
+
+
+def attn_ref(q, k, v, scale, mask=None):
+    """q [B, H, nq, d], k / v [B, H, nk, d], mask broadcastable to [B, H, nq, nk] (additive) -> fp64 [B, H, nq, d]"""
+    s = torch.einsum("bhid,bhjd->bhij", q.double(), k.double()) * scale
+    if mask is not None:
+        s = s + mask.double()
+    return torch.einsum("bhij,bhjd->bhid", s.softmax(-1), v.double())
+
+
+def softmax_ref(x):
+    return x.double().softmax(-1)
+
+
+def timestep_ref(t, dim, max_period=10000.0, swap=False):
+    """cat([cos, sin]) of t * exp(-ln(P) k / half); the argument is formed in fp32 as the kernel does (the rounding of t * freq is part of
+    the operation at t ~ 1e5, not kernel error), the cos / sin in fp64.  swap: sin first (planted bug)."""
+    half = dim // 2
+    freqs = torch.exp(-math.log(max_period) * torch.arange(half, dtype=torch.float64) / half).float()
+    a = (t.float().cpu()[:, None] * freqs[None]).double()
+    c, s = torch.cos(a), torch.sin(a)
+    return torch.cat([s, c] if swap else [c, s], -1)
+
+
+def silu_ref(x):
+    x = x.double()
+    return x * torch.sigmoid(x)
+
+
+def act_ref(x, kind, quick_gelu_coef=1.702):
+    x = x.double()
+    if kind == 0:
+        return x * torch.sigmoid(quick_gelu_coef * x)
+    if kind == 1:
+        return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
+    return x.clamp_min(0.0)
+
+
+def sample_posterior_ref(moments, ld, noise, lc, scale, shift, clamp=True):
+    """moments [B * npix, ld] (mean | logvar in the first 2 lc columns), noise fp32 [B, lc, h, w] -> fp64 [B, lc, h, w]"""
+    b, _, hh, ww = noise.shape
+    m = moments.double().reshape(b, hh * ww, ld)
+    mean = m[..., :lc].permute(0, 2, 1).reshape(b, lc, hh, ww)
+    logvar = m[..., lc:2 * lc].permute(0, 2, 1).reshape(b, lc, hh, ww)
+    if clamp:
+        logvar = logvar.clamp(-30.0, 20.0)
+    return (mean + torch.exp(0.5 * logvar) * noise.double() - shift) * scale
+
+
+def pack_latent_ref(z, scaling_factor, shift, ld):
+    """z fp32 NCHW -> [B, H, W, ld] fp64 (columns >= C zero); the kernel divides in fp32, so the reference rounds that quotient to fp32"""
+    b, c, h, w = z.shape
+    out = torch.zeros(b, h, w, ld, dtype=torch.float64)
+    out[..., :c] = ((z.float().cpu() / scaling_factor).double() + shift).permute(0, 2, 3, 1)
+    return out
+
+
+def unpack_image_ref(y, ld, c):
+    return ((y.double().reshape(-1, ld)[:, :c] + 1.0) / 2.0).clamp(0.0, 1.0)
+
+
+def count_nonfinite_ref(bits, high_half_ignored=False):
+    """bits: int16 / uint16 view of fp16 data -> number of inf / NaN (exponent all ones).  high_half_ignored: the planted bug of a vector
+    body that tests only the low 16 bits of each 32-bit word (elements at odd indices of full 8-vectors are never looked at)."""
+    b = bits.to(torch.int32) & 0xFFFF
+    bad = (b & 0x7C00) == 0x7C00
+    if high_half_ignored:
+        n = b.numel()
+        full = (n // 8) * 8
+        idx = torch.arange(n)
+        bad = bad & ~((idx < full) & (idx % 2 == 1))
+    return int(bad.sum())
+
+
+def add_scaled_ref(h, c, alpha, skip_tail=False):
+    """h fp16 (flat) + alpha * c -> fp64; skip_tail: the planted bug that leaves the last partial 8-vector unchanged"""
+    out = h.double() + alpha * c.double()
+    if skip_tail:
+        full = (h.numel() // 8) * 8
+        out.view(-1)[full:] = h.double().view(-1)[full:]
+    return out
+
+
+def add_control_nchw_ref(h, ctrl):
+    """h NHWC fp16 + ctrl NCHW fp32 -> NHWC fp64"""
+    return h.double() + ctrl.double().permute(0, 2, 3, 1)
+
+
+def avgpool_ref(x):
+    n, h, w, c = x.shape
+    return x.double().reshape(n, h // 2, 2, w // 2, 2, c).mean((2, 4))
+
+
+def embed_ref(ids, tok, pos):
+    b, t = ids.shape
+    return (tok.double()[ids.long()] + pos.double()[:t][None]).reshape(b * t, -1)
+
+
+def layernorm_ref(x, gamma, beta, eps):
+    return F.layer_norm(x.double(), (x.shape[-1],), gamma.double(), beta.double(), eps)
+
+
+def blend_ref(a, am, b, bm):
+    return a.double() * am.double() + b.double() * bm.double()
+
+
+def strided_ref(src, dims, src_strides, dst_dtype):
+    """the elements fmx_strided_copy4 writes, in destination index order [d0, d1, d2, d3], converted by torch: a bool source becomes
+    0 / -inf; other sources convert through fp32 (the kernel's intermediate) to dst_dtype"""
+    flat = src.reshape(-1).cpu()
+    idx = torch.zeros(dims, dtype=torch.long)
+    for i, (d, s) in enumerate(zip(dims, src_strides)):
+        shape = [1, 1, 1, 1]
+        shape[i] = d
+        idx = idx + (torch.arange(d) * s).reshape(shape)
+    v = flat[idx]
+    if v.dtype == torch.bool:
+        v = torch.where(v, torch.tensor(0.0), torch.tensor(-math.inf))
+    return v.float().to(dst_dtype)

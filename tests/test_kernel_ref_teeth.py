@@ -1,0 +1,265 @@
+"""CPU: the kernel-level GPU tests have teeth.  For each test in tests/test_gpu_kernels_bf16.py and tests/test_gpu_small_kernels.py, one
+plausible subtle bug is planted into the fp64 reference (tests/kernel_refs.py) and evaluated on that test's own inputs; the planted result must
+lie outside the GPU test's tolerance by at least 4x (kernel_refs.excess >= 4), or -- for the exact tests -- differ in at least 4 places.
+Runs without a GPU, so a tolerance too loose to catch anything fails before anyone gets a GPU."""
+import math
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+import kernel_refs as R
+import test_gpu_kernels_bf16 as B
+import test_gpu_small_kernels as S
+
+BF, H16 = torch.bfloat16, torch.float16
+TEETH = 4.0
+
+
+def bites(planted, want, dtype, tol, what):
+    e = R.excess(planted, want, dtype, *tol)
+    assert e >= TEETH, f"{what}: the planted bug is only {e:.3g}x the tolerance"
+
+
+# ---- bf16 file ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["down_even", "down_odd"])
+def test_conv_downsample_pad_on_the_wrong_side_is_caught(case):
+    """planted: the Downsample's zero row / column taken at the top / left instead of bottom / right (a one-pixel border shift)"""
+    cfg = B.CONV_CASES[case]
+    x, x1, wt, bias, res, _ = B.conv_case(cfg)
+    want = B.conv_case_ref(cfg, x, x1, wt, bias, res)
+    xin = F.pad(x.double().permute(0, 3, 1, 2), (1, 0, 1, 0))
+    planted = F.conv2d(xin, wt.double(), bias.double(), stride=2).permute(0, 2, 3, 1) + res.double().reshape(want.shape)
+    bites(planted, want, BF, R.CONV_TOL[BF], case)
+
+
+def test_conv_up_on_load_off_by_one_is_caught():
+    """planted: nearest upsample on load reading source row (y + 1) // 2 instead of y // 2"""
+    cfg = B.CONV_CASES["up_ragged"]
+    x, x1, wt, bias, res, _ = B.conv_case(cfg)
+    want = B.conv_case_ref(cfg, x, x1, wt, bias, res)
+    uh, uw = cfg["up"]
+    iy = ((torch.arange(uh) + 1) // 2).clamp(max=cfg["h"] - 1)
+    ix = ((torch.arange(uw) + 1) // 2).clamp(max=cfg["w"] - 1)
+    xu = x[:, iy][:, :, ix]
+    planted = R.conv_ref(xu, wt, bias, pad=1, residual=res)
+    bites(planted, want, BF, R.CONV_TOL[BF], "up on load")
+
+
+def test_groupnorm_eps_1e5_instead_of_1e6_is_caught():
+    n, hh, ww, cin, c = 2, 16, 16, 64, 128
+    x, wt, bias, gamma, beta = B.gn_conv_inputs(n, hh, ww, cin, c, seed=40)
+    out = R.conv_ref(x, wt, bias, pad=1).to(BF)      # stands in for the stored bf16 output
+    want = R.groupnorm_ref(out, gamma, beta, 1e-6, silu=True)
+    bites(R.groupnorm_ref(out, gamma, beta, 1e-5, silu=True), want, BF, R.GN_TOL[BF], "GroupNorm eps")
+
+
+def test_groupnorm_statistics_missing_a_chunk_is_caught():
+    """planted: the last chunk's partials dropped from the sums (relative 2e-5 tolerance of the statistics check)"""
+    n, hh, ww, cin, c = 2, 10, 10, 64, 512
+    x, wt, bias, _, _ = B.gn_conv_inputs(n, hh, ww, cin, c, seed=40)
+    out = R.conv_ref(x, wt, bias, pad=1).to(BF).reshape(n * hh * ww, c)
+    want = R.stat_sums_ref(out, n)
+    planted = R.stat_sums_ref(out.view(n, hh * ww, c)[:, :-32].reshape(-1, c), n)
+    with pytest.raises(AssertionError):
+        torch.testing.assert_close(planted, want, rtol=2e-5, atol=2e-3)
+
+
+def test_groupnorm_large_offset_mean_rounded_to_bf16_is_caught():
+    """planted: the group mean rounded to bf16 before it is subtracted (ulp 16 at 3000: a shift of ~0.1 standard deviation)"""
+    n, h, w, c = 1, 16, 16, 320
+    x = (torch.randn(n, h, w, c, generator=B.gen(320)) * 100 + 3000).to(BF)
+    g, b = (1 + 0.1 * torch.randn(c, generator=B.gen(321))).to(BF), (0.1 * torch.randn(c, generator=B.gen(322))).to(BF)
+    want = R.groupnorm_ref(x, g, b, 1e-5)
+    xg = x.double().reshape(n, h * w, 32, c // 32)
+    mean = xg.mean((1, 3), keepdim=True)
+    var = ((xg - mean) ** 2).mean((1, 3), keepdim=True)
+    planted = ((xg - mean.to(BF).double()) / torch.sqrt(var + 1e-5)).reshape(n, h, w, c) * g.double() + b.double()
+    bites(planted, want, BF, R.GN_TOL[BF], "GroupNorm mean rounded")
+
+
+def test_attention512_padded_keys_not_masked_is_caught():
+    b, n, nk, c = 3, 200, 77, 512
+    nkp = -(-nk // 32) * 32
+    q = B.rnd(b * n, c, seed=121).view(b, 1, n, c)
+    k = torch.full((b, nkp, c), 7.0, dtype=BF)
+    v = torch.full((b, nkp, c), -5.0, dtype=BF)
+    k[:, :nk], v[:, :nk] = B.rnd(b, nk, c, seed=122), B.rnd(b, nk, c, seed=123)
+    k[b - 1, nk - 1] = q[b - 1, 0, n - 1] * 0.5
+    want = R.attn_ref(q, k[:, None, :nk], v[:, None, :nk], c ** -0.5)
+    bites(R.attn_ref(q, k[:, None], v[:, None], c ** -0.5), want, BF, R.ATTN_TOL[BF], "512-wide attention over padded keys")
+
+
+@pytest.mark.parametrize("dtype", [H16, BF])
+def test_softmax_sum_over_the_padding_columns_is_caught(dtype):
+    rows, n, ld = 64, 77, 128
+    s = torch.full((rows, ld), 30.0, dtype=dtype)
+    s[:, :n] = (torch.randn(rows, n, generator=B.gen(60)) * 3).to(dtype)
+    want = R.softmax_ref(s[:, :n])
+    bites(R.softmax_ref(s)[:, :n], want, dtype, R.SOFTMAX_TOL[dtype], "softmax over ld columns")
+
+
+def test_t5_bias_of_head_0_for_every_head_is_caught():
+    """planted: the mask's head stride ignored (mask_hs treated as 0): every head gets head 0's position bias"""
+    b, heads, d, t = 2, 4, 64, 77
+    c, tp = heads * d, 128
+    qk = B.rnd(b, t, 2 * c, scale=1.2, seed=200 + t)
+    v = B.rnd(b, t, c, seed=300 + t)
+    bias = B.t5_bias(heads, t, tp, seed=400 + t)
+    q = qk[..., :c].view(b, t, heads, d).permute(0, 2, 1, 3)
+    k = qk[..., c:].view(b, t, heads, d).permute(0, 2, 1, 3)
+    vv = v.view(b, t, heads, d).permute(0, 2, 1, 3)
+    want = R.attn_ref(q, k, vv, 1.0, mask=bias[None, :, :, :t])
+    planted = R.attn_ref(q, k, vv, 1.0, mask=bias[None, :1, :, :t])
+    bites(planted, want, BF, R.ATTN_TOL[BF], "T5 bias head stride")
+
+
+def test_d64_scale_folded_twice_is_caught():
+    """planted: 1/sqrt(d) applied to the scores twice (e.g. once folded into log2(e) and once by the caller)"""
+    b, h, nq, nk, d = 2, 4, 512, 77, 64
+    q = B.rnd(b, nq, h, d, seed=500).permute(0, 2, 1, 3)
+    k, v = B.rnd(b, nk, h, d, seed=501).permute(0, 2, 1, 3), B.rnd(b, nk, h, d, seed=502).permute(0, 2, 1, 3)
+    want = R.attn_ref(q, k, v, d ** -0.5)
+    bites(R.attn_ref(q, k, v, d ** -1.0), want, BF, R.ATTN_TOL[BF], "d64 scale")
+
+
+def test_silu_tail_left_unwritten_is_caught():
+    """planted: the elements past the last full 256-thread block (4096..4099) never written (zero)"""
+    x = (torch.randn(4099, generator=B.gen(70)) * 6).to(BF)
+    want = R.silu_ref(x)
+    planted = want.clone()
+    planted[4096:] = 0.0
+    bites(planted, want, BF, R.ELEM_TOL[BF], "silu tail")
+
+
+@pytest.mark.parametrize("dtype", [H16, BF])
+def test_timestep_embedding_cos_sin_swapped_is_caught(dtype):
+    t = torch.tensor([0.0, 1.0, 3.5, 999.0, 1000.0, 3500.0, 10000.0, 417.25])
+    bites(R.timestep_ref(t, 256, swap=True), R.timestep_ref(t, 256), dtype, R.TEMB_TOL[dtype], "cos / sin swapped")
+
+
+def test_vae_pack_shift_before_division_and_unpack_without_clamp_are_caught():
+    z = torch.randn(2, 16, 5, 7, generator=B.gen(80)) * 3
+    want = R.pack_latent_ref(z, 0.3611, 0.1159, 20)
+    planted = torch.zeros_like(want)
+    planted[..., :16] = ((z.double() + 0.1159) / 0.3611).permute(0, 2, 3, 1)
+    bites(planted[..., :16], want[..., :16], BF, R.ELEM_TOL[BF], "pack: (z + shift) / sf")
+    y = (torch.randn(70, 4, generator=B.gen(81)) * 1.5).to(BF)
+    bites((y.double()[:, :3] + 1.0) / 2.0, R.unpack_image_ref(y, 4, 3), torch.float32, R.F32_TOL, "unpack: no clamp")
+
+
+# ---- small-kernel file ------------------------------------------------------------------------------------------------------------------
+def test_quick_gelu_coefficient_1_7_is_caught():
+    x = torch.randn(4099, generator=S.gen(1)) * 4
+    x[:17] = S.f16_extremes().float()
+    x = x.half()
+    bites(R.act_ref(x, 0, quick_gelu_coef=1.7), R.act_ref(x, 0), H16, S.ACT_TOL[0], "quick-GELU 1.7")
+
+
+def test_erf_gelu_as_tanh_approximation_is_caught():
+    x = (torch.randn(4099, generator=S.gen(1)) * 4).half()
+    planted = F.gelu(x.double(), approximate="tanh")
+    bites(planted, R.act_ref(x, 1), H16, S.ACT_TOL[1], "erf-GELU as tanh-GELU")
+
+
+def test_relu_dropping_nan_is_caught():
+    x = torch.tensor([1.0, -1.0, math.nan, math.nan, math.nan, math.nan]).half()
+    assert R.excess(torch.nan_to_num(R.act_ref(x, 2), nan=0.0), R.act_ref(x, 2), H16, 1.0, 0.0) == math.inf
+
+
+def test_avgpool_window_shifted_by_one_column_is_caught():
+    x = (torch.randn(2, 6, 10, 13, generator=S.gen(2)) * 3).half()
+    xs = torch.cat([x[:, :, 1:], x[:, :, -1:]], 2)
+    bites(R.avgpool_ref(xs), R.avgpool_ref(x), H16, R.ELEM_TOL[H16], "avgpool column shift")
+
+
+def test_embed_position_off_by_one_is_caught():
+    b, t, c, vocab = 3, 77, 768, 1000
+    ids = torch.randint(0, vocab, (b, t), generator=S.gen(3), dtype=torch.int32)
+    tok = (torch.randn(vocab, c, generator=S.gen(4)) * 0.02).half()
+    pos = (torch.randn(t, c, generator=S.gen(5)) * 0.01).half()
+    planted = R.embed_ref(ids, tok, torch.cat([pos[1:], pos[-1:]]))
+    bites(planted, R.embed_ref(ids, tok, pos), H16, R.ELEM_TOL[H16], "embed position + 1")
+
+
+def test_cast_round_toward_zero_is_caught():
+    x = torch.randn(1001, generator=S.gen(6)) * 1000
+    want = x.half()
+    wb = want.view(torch.int16)
+    planted = torch.where(want.float().abs() > x.abs(), wb - 1, wb)     # one fp16 step toward zero where RNE rounded away from it
+    assert int((planted != wb).sum()) >= TEETH
+
+
+def test_scale_by_reciprocal_division_is_caught():
+    x = torch.randn(1003, generator=S.gen(7)) * 100
+    s = torch.tensor(0.18215, dtype=torch.float32)
+    assert int((x / (1.0 / s) != x * s).sum()) >= TEETH
+
+
+@pytest.mark.parametrize("n", [4096, 100003])
+def test_count_nonfinite_ignoring_the_high_half_word_is_caught(n):
+    g = S.gen(8)
+    x = (torch.randn(n, generator=g) * 100).half()
+    bits = x.view(torch.int16)
+    pos = sorted(set([1, 2, 3, n - 2, n - 3] + torch.randint(0, n, (min(n, 40),), generator=g).tolist()) - {0, n - 1, n // 2})
+    for p in pos:
+        bits[p] = 0x7C00
+    assert R.count_nonfinite_ref(bits) - R.count_nonfinite_ref(bits, high_half_ignored=True) >= TEETH
+
+
+def test_sample_posterior_unclamped_logvar_is_caught():
+    b, lc, hh, ww, ld = 2, 4, 5, 7, 16
+    g = S.gen(9)
+    mo = torch.randn(b * hh * ww, ld, generator=g)
+    lv = torch.tensor([-40.0, -30.5, -30.0, -29.5, -3.0, 0.0, 5.0, 19.5, 20.0, 20.5, 25.0, 11.0])
+    mo[:, lc:2 * lc] = lv[torch.randint(0, lv.numel(), (b * hh * ww, lc), generator=g)]
+    mo = mo.half()
+    noise = torch.randn(b, lc, hh, ww, generator=g)
+    want = R.sample_posterior_ref(mo, ld, noise, lc, 0.18215, 0.0)
+    bites(R.sample_posterior_ref(mo, ld, noise, lc, 0.18215, 0.0, clamp=False), want, torch.float32, R.F32_TOL, "logvar unclamped")
+
+
+def test_blend_with_the_wrong_mask_is_caught():
+    n = 4099
+    g = S.gen(10)
+    a, b = torch.randn(n, generator=g) * 4, torch.randn(n, generator=g) * 4
+    am = (torch.rand(n, generator=g) > 0.5).float() * torch.rand(n, generator=g)
+    bm = 1.0 - am
+    atol = 2.0 ** -24 * float((a.abs() * am + b.abs() * bm).max())
+    bites(R.blend_ref(a, am, b, am), R.blend_ref(a, am, b, bm), torch.float32, (1.0, atol), "blend b * a_mask")
+
+
+def test_add_scaled_last_partial_vector_skipped_is_caught():
+    b, hh, ww, c = 1, 5, 3, 13          # 195 elements: a 3-element tail
+    g = S.gen(11)
+    h = (torch.randn(b, hh, ww, c, generator=g) * 2).half()
+    ctrl = torch.randn(b, hh, ww, c, generator=g).half()
+    bites(R.add_scaled_ref(h, ctrl, 0.7, skip_tail=True), R.add_scaled_ref(h, ctrl, 0.7), H16, R.ELEM_TOL[H16], "tail skipped")
+
+
+def test_add_control_nchw_read_as_nhwc_is_caught():
+    b, c, hh, ww = 3, 100, 7, 10
+    g = S.gen(13)
+    h = (torch.randn(b, hh, ww, c, generator=g) * 2).half()
+    ctrl = torch.randn(b, c, hh, ww, generator=g) * 0.75
+    planted = h.double() + ctrl.double().reshape(b, hh, ww, c)
+    bites(planted, R.add_control_nchw_ref(h, ctrl), H16, R.ELEM_TOL[H16], "NCHW read as NHWC")
+
+
+def test_layernorm_eps_outside_the_sqrt_is_caught():
+    c = 1280
+    g = S.gen(14)
+    rs = torch.exp(torch.empty(2000, 1).uniform_(math.log(1e-2), math.log(3.0), generator=g))
+    x = (torch.randn(2000, c, generator=g) * rs + 0.5 * rs).half()
+    gm, bt = (1 + 0.1 * torch.randn(c, generator=g)).half(), (0.1 * torch.randn(c, generator=g)).half()
+    xd = x.double()
+    mu, sd = xd.mean(-1, keepdim=True), xd.var(-1, unbiased=False, keepdim=True).sqrt()
+    planted = (xd - mu) / (sd + 1e-5) * gm.double() + bt.double()
+    bites(planted, R.layernorm_ref(x, gm, bt, 1e-5), H16, (2.0, 2 * R.EPS[H16]), "layernorm eps outside sqrt")
+
+
+def test_bool_mask_as_one_zero_is_caught():
+    m = torch.rand(5, 77, generator=S.gen(16)) > 0.5
+    want = R.strided_ref(m, (1, 1, 5, 77), (0, 0, 77, 1), H16)
+    planted = m.half().reshape(1, 1, 5, 77)
+    assert int((planted.view(torch.int16) != want.view(torch.int16)).sum()) >= TEETH
