@@ -203,11 +203,14 @@ typedef struct fmx_attn_args {
   int64_t o_bs, o_rs;
   int32_t batch, heads, nq, nk, nk_pad, dpad;
   float scale;
-  int32_t causal; /* 1: key j attends only for j <= query i (CLIP text encoder, transformers causal mask); occupies former padding */
+  int32_t causal; /* 1: key j attends only for j <= query i (CLIP text encoder, transformers causal mask), nq == nk; occupies former padding */
   const void* zero_page;
   /* optional additive mask (attention_function's `mask`, backend/attention.py:74-88 / SDPA attn_mask): fp16, added to the score before the
    * softmax, element (b, h, i, j) at mask[b*mask_bs + h*mask_hs + i*mask_qs + j]; a stride of 0 broadcasts that dimension; every addressed row
-   * holds nk_pad keys; 16-byte aligned, strides % 8 == 0.  -inf entries mask a key out (a bool mask is converted by fmx_strided_copy4). */
+   * holds nk_pad keys; 16-byte aligned, strides % 8 == 0.  -inf entries mask a key out (a bool mask is converted by fmx_strided_copy4); the
+   * pad columns [nk, nk_pad) of a row are ignored, whatever they hold (NaN and +-inf included).  A query row in which no key attends (every
+   * mask entry -inf, alone or together with `causal`) gives 0, as torch's scaled_dot_product_attention does; leading key tiles that are
+   * entirely -inf are harmless. */
   const void* mask;
   int64_t mask_bs, mask_hs, mask_qs;
 } fmx_attn_args;

@@ -173,9 +173,19 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) sacc[s][r] += (float)(r < 8 ? m0[r & 7] : m1[r & 7]) * p.inv_scale;
       }
+      // the mask's pad columns [nk, nk_pad) may hold anything (NaN, +inf): the ragged tail is masked again after the add, so that the -inf
+      // set above is not turned into NaN.  Done here rather than by moving the tail masking below the add: that order costs the unmasked
+      // path 20 VGPRs (attn_kernel<48>: 121 -> 141, 3 -> 2 waves per SIMD, +9 % at SD1.5's 4096-token self-attention).
+      if ((kt + 1) * KVB > p.nk) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (kt * KVB + s * 32 + hi * 16 + r >= p.nk) sacc[s][r] = -INFINITY;
+      }
     }
-    if (p.causal && (kt + 1) * KVB - 1 > q0) {  // causal mask (CLIP text encoder): key j > query i never attends; the first key
-      const int qi = q0 + li;                   // tile always holds key 0 <= i, so the running max is finite from tile 0 on
+    if (p.causal && (kt + 1) * KVB - 1 > q0) {  // causal mask (CLIP text encoder): key j > query i never attends
+      const int qi = q0 + li;
 #pragma unroll
       for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -189,8 +199,11 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
       for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[s][r]);
     mx = fmaxf(mx, __shfl_xor(mx, 32));
     const float m_new = fmaxf(m_run, mx);
-    const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c2);
-    const float mc = m_new * c2;
+    // a row whose keys so far are all masked (a -inf mask over the leading tiles) has m_new == -inf: exponentiate against 0 instead, so that
+    // alpha = exp2(-inf) = 0 and every e = exp2(-inf) = 0 rather than exp2(-inf - -inf) = NaN
+    const float m_ref = m_new == -INFINITY ? 0.f : m_new;
+    const float alpha = __builtin_amdgcn_exp2f((m_run - m_ref) * c2);
+    const float mc = m_ref * c2;
     float psum = 0.f;
     f16x8 pf[2][2];
 #pragma unroll
@@ -230,7 +243,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
 
   // ---- finish: 1/l, store O[b][q][h*DP + d]; lane = query, registers = 4-wide runs of d --------------------
   const float l_tot = l_run + __shfl_xor(l_run, 32);
-  const float inv = 1.0f / l_tot;
+  const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;   // no key attends (a fully masked row): 0, as torch's SDPA returns it
   const int qg = q0 + li;
   if (qg < p.nq) {
     f16* op = p.o + (long)b * p.o_bs + (long)qg * p.o_rs + (long)h * DP;

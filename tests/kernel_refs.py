@@ -100,12 +100,18 @@ def stat_sums_ref(out, n):
     return torch.stack([o.sum(1), (o * o).sum(1)], -1)
 
 
-def attn_ref(q, k, v, scale, mask=None):
-    """q [B, H, nq, d], k / v [B, H, nk, d], mask broadcastable to [B, H, nq, nk] (additive) -> fp64 [B, H, nq, d]"""
+def attn_ref(q, k, v, scale, mask=None, causal=False):
+    """q [B, H, nq, d], k / v [B, H, nk, d], mask broadcastable to [B, H, nq, nk] (additive) -> fp64 [B, H, nq, d].  causal: key j > query i
+    never attends.  A row with no attending key (every score -inf) is 0, as torch's scaled_dot_product_attention returns it."""
     s = torch.einsum("bhid,bhjd->bhij", q.double(), k.double()) * scale
     if mask is not None:
         s = s + mask.double()
-    return torch.einsum("bhij,bhjd->bhid", s.softmax(-1), v.double())
+    if causal:
+        nq, nk = s.shape[-2:]
+        s = s.masked_fill(torch.ones(nq, nk, dtype=torch.bool, device=s.device).triu(1), -math.inf)
+    dead = ~(s > -math.inf).any(-1, keepdim=True)
+    p = torch.where(dead, torch.zeros((), dtype=s.dtype, device=s.device), s.softmax(-1))
+    return torch.einsum("bhij,bhjd->bhid", p, v.double())
 
 
 def softmax_ref(x):

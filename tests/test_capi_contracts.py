@@ -172,3 +172,26 @@ def test_host_tensors_and_mixed_element_types_are_rejected_not_converted():
         ops.silu(torch.zeros(8))                           # fp32 on the host
     with pytest.raises(TypeError):
         ops.layernorm_mod(x, w.bfloat16(), w, 64)
+
+
+@pytest.mark.parametrize("suffix", ["_f16", "_bf16"])
+def test_attention_mask_and_causal_contracts(lib, suffix):
+    """the generic attention kernel's causal flag needs nq == nk; the additive mask is read as 16-byte vectors: 16-byte aligned base, strides
+    that are multiples of 8 elements"""
+    fn = getattr(lib, "fmx_attention" + suffix)
+    err = lambda: lib.fmx_last_error().decode()  # noqa: E731
+
+    def args(**kw):
+        a = AttnArgs()
+        a.q = a.k = a.vt = a.o = a.zero_page = FAKE
+        a.batch, a.heads, a.nq, a.nk, a.nk_pad, a.dpad, a.scale = 2, 2, 77, 77, 128, 48, 0.1
+        a.q_bs, a.q_rs, a.k_bs, a.k_rs, a.vt_bs, a.vt_hs, a.vt_ds, a.o_bs, a.o_rs = 77 * 96, 96, 128 * 96, 96, 128, 48 * 256, 256, 77 * 96, 96
+        for k_, v_ in kw.items():
+            setattr(a, k_, v_)
+        return C.byref(a)
+    assert fn(args(causal=1, nq=100), None) == BADARG and "nq == nk" in err()
+    assert fn(args(causal=1, nk=50), None) == BADARG and "nq == nk" in err()
+    assert fn(args(mask=FAKE + 8, mask_qs=128), None) == BADARG and "16-byte aligned" in err()
+    for strides in ((0, 0, 100), (0, 12, 128), (4, 0, 0)):
+        bs, hs, qs = strides
+        assert fn(args(mask=FAKE, mask_bs=bs, mask_hs=hs, mask_qs=qs), None) == BADARG and "multiples of 8" in err(), strides

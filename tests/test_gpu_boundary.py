@@ -12,6 +12,8 @@ import forge_amd  # noqa: E402,F401
 from forge_amd.backend import attention as fattn  # noqa: E402
 from forge_amd.backend import operations as fops  # noqa: E402
 
+import kernel_refs as R  # noqa: E402
+
 DEV = "cuda"
 
 
@@ -73,6 +75,41 @@ def test_attention_function_masks():
     km = torch.ones(b, nk, dtype=torch.bool, device=DEV)
     km[:, 40:] = False
     close(fattn.attention_function(q2, k, v, heads, mask=km), _ref(q2, k[:, :40], v[:, :40], heads), 2e-3, 2e-3, "key mask == truncated keys")
+
+
+def _sdpa64(q, k, v, heads, mask):
+    """fp64 scaled_dot_product_attention on the CPU (the reference's attention_pytorch) on the fp16 q / k / v and the fp16-rounded mask, 4-D"""
+    b, nq, hd = q.shape
+    sp = lambda t: t.double().cpu().view(b, -1, heads, hd // heads).transpose(1, 2)  # noqa: E731
+    m = mask.cpu() if mask.dtype == torch.bool else mask.half().double().cpu()
+    return F.scaled_dot_product_attention(sp(q), sp(k), sp(v), attn_mask=m)
+
+
+@pytest.mark.parametrize("d", [40, 64, 80, 160])
+def test_attention_function_masks_without_a_visible_prefix(d):
+    """Masks that leave the leading key tiles or whole rows with nothing to attend to: left-padded bool key masks hiding the first 64 and 100
+    tokens, an fp32 [B, Nq, Nk] bias whose masked entries are finfo(float32).min (fp16 -inf after the conversion), covering the first 64
+    keys of every other query, and a bool [B, heads, Nq, Nk] mask with fully masked query rows (0 there, as SDPA returns).  Against fp64 SDPA; ATTN_TOL."""
+    b, heads, nq, nk = 2, 4, 200, 160
+    q, k, v = rnd(b, nq, heads * d, seed=30), rnd(b, nk, heads * d, seed=31), rnd(b, nk, heads * d, seed=32)
+    g = torch.Generator("cpu").manual_seed(33)
+    masks = {}
+    for hide in (64, 100):
+        km = torch.ones(b, nk, dtype=torch.bool)
+        km[:, :hide] = False
+        masks[f"key mask hiding {hide}"] = (km.to(DEV), km[:, None, None, :])
+    fm = torch.where(torch.rand(b, nq, nk, generator=g) < 0.4, torch.finfo(torch.float32).min, 0.0)
+    fm[:, ::2, :64] = torch.finfo(torch.float32).min
+    fm = torch.where(fm == 0, torch.randn(b, nq, nk, generator=g), fm)          # a finite bias on the keys that attend
+    masks["fp32 finfo.min"] = (fm.to(DEV), fm[:, None])
+    full = torch.rand(b, heads, nq, nk, generator=g) > 0.3
+    full[:, :, ::7] = False
+    full[1, 2, 1] = False
+    masks["bool rows fully masked"] = (full.to(DEV), full)
+    for what, (m, m4) in masks.items():
+        got = fattn.attention_function(q, k, v, heads, mask=m).view(b, nq, heads, d).transpose(1, 2)
+        want = _sdpa64(q, k, v, heads, m4)
+        R.assert_within(got, want, torch.float16, *R.ATTN_TOL[torch.float16], f"attention_function d{d}: {what}")
 
 
 @pytest.mark.parametrize("c,hh,ww", [(512, 16, 24), (128, 16, 16), (512, 32, 32)])

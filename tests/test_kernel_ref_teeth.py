@@ -1,4 +1,5 @@
-"""CPU: the kernel-level GPU tests have teeth.  For each test in tests/test_gpu_kernels_bf16.py and tests/test_gpu_small_kernels.py, one
+"""CPU: the kernel-level GPU tests have teeth.  For each test in tests/test_gpu_kernels_bf16.py, tests/test_gpu_small_kernels.py and each test
+family of tests/test_gpu_attention_generic.py, one
 plausible subtle bug is planted into the fp64 reference (tests/kernel_refs.py) and evaluated on that test's own inputs; the planted result must
 lie outside the GPU test's tolerance by at least 4x (kernel_refs.excess >= 4), or -- for the exact tests -- differ in at least 4 places.
 Runs without a GPU, so a tolerance too loose to catch anything fails before anyone gets a GPU."""
@@ -9,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 import kernel_refs as R
+import test_gpu_attention_generic as G
 import test_gpu_kernels_bf16 as B
 import test_gpu_small_kernels as S
 
@@ -263,3 +265,64 @@ def test_bool_mask_as_one_zero_is_caught():
     want = R.strided_ref(m, (1, 1, 5, 77), (0, 0, 77, 1), H16)
     planted = m.half().reshape(1, 1, 5, 77)
     assert int((planted.view(torch.int16) != want.view(torch.int16)).sum()) >= TEETH
+
+
+# ---- generic attention file -------------------------------------------------------------------------------------------------------------
+def _tri(t, keep):
+    """additive [1, 1, t, nk_pad(t)] mask: 0 where keep(i, j), -inf elsewhere"""
+    i, j = torch.arange(t)[:, None], torch.arange(G.nkpad(t))[None, :]
+    return torch.where(keep(i, j), 0.0, -math.inf)[None, None]
+
+
+@pytest.mark.parametrize("keep,what", [(lambda i, j: j < i, "causal diagonal excluded"), (lambda i, j: j <= i + 1, "causal off by one")])
+def test_causal_boundary_bugs_are_caught(keep, what):
+    t, d = 77, 64
+    _, _, q, k, v = G.clip_case(t, 12, H16)
+    want = G.reference(q, k, v, t, d, causal=True, dev="cpu")
+    bites(G.reference(q, k, v, t, d, mask=_tri(t, keep), dev="cpu"), want, H16, R.ATTN_TOL[H16], what)
+
+
+@pytest.mark.parametrize("dtype", [H16, BF])
+def test_mask_stride_bugs_are_caught(dtype):
+    """planted on the all-strides case: the query stride ignored (row 0 for every query), the batch stride ignored (batch 0's mask for every
+    batch), the mask multiplied by the score scale (added after the scaling of the unscaled score instead of divided by it)"""
+    d = 80
+    mask, q, k, v, _ = G.mask_case(7, d, dtype)
+    want = G.reference(q, k, v, G.MASK_NK, d, mask=mask, dev="cpu")
+    tol = R.ATTN_TOL[dtype]
+    bites(G.reference(q, k, v, G.MASK_NK, d, mask=mask[:, :, :1], dev="cpu"), want, dtype, tol, "mask query stride ignored")
+    bites(G.reference(q, k, v, G.MASK_NK, d, mask=mask[:1], dev="cpu"), want, dtype, tol, "mask batch stride ignored")
+    scaled = (mask.double() * d ** -0.5).to(dtype)
+    bites(G.reference(q, k, v, G.MASK_NK, d, mask=scaled, dev="cpu"), want, dtype, tol, "mask scaled with the scores")
+
+
+def test_scale_from_dpad_is_caught():
+    """planted: 1 / sqrt(48) for d_head 40 (the padded width); on the first head of the SD1.5 cross-attention case"""
+    b, h, nq, nk, d = 8, 8, 4096, 77, 40
+    q, k, v = G.sd15_case(b, h, nq, nk, d)
+    q1, k1, v1 = (t[:1, :, :1, :d].permute(0, 2, 1, 3) for t in (q, k[:, :nk], v[:, :nk]))
+    want = R.attn_ref(q1, k1, v1, d ** -0.5)
+    bites(R.attn_ref(q1, k1, v1, G.DPAD[d] ** -0.5), want, H16, R.ATTN_TOL[H16], "scale from dpad")
+
+
+def test_nan_after_a_masked_leading_tile_is_caught():
+    """planted: the rows whose first key tile is fully masked come out NaN (alpha = exp2(-inf - -inf))"""
+    d = 40
+    mask, q, k, v, _ = G.neg_inf_case("lead_128_some_queries", d, H16)
+    want = G.reference(q, k, v, G.INF_NK, d, mask=mask, dev="cpu")
+    lead = (mask[..., :64] == -math.inf).all(-1)[:, 0]                       # [B, nq]
+    planted = want.clone()
+    planted.permute(0, 2, 1, 3)[lead] = math.nan
+    assert bool(lead.any())
+    bites(planted, want, H16, R.ATTN_TOL[H16], "NaN rows after a masked leading tile")
+
+
+def test_mask_pad_columns_added_is_caught():
+    """planted: the ragged-tail -inf set before the mask is added, so the NaN / +inf of the mask's pad columns reach the scores"""
+    d = 64
+    mask, q, k, v, _ = G.neg_inf_case("pad_nan_inf", d, H16)
+    nk, nkp = G.INF_NK, G.nkpad(G.INF_NK)
+    want = G.reference(q, k, v, nk, d, mask=mask, dev="cpu")
+    leaked = mask.double().clone()
+    leaked[..., nk:] = -math.inf + leaked[..., nk:]
+    bites(G.reference(q, k, v, nkp, d, mask=leaked, dev="cpu"), want, H16, R.ATTN_TOL[H16], "mask pad columns added")
