@@ -43,6 +43,8 @@
  *   fmx_embed_tokens       CLIP token + position embedding (transformers CLIPTextEmbeddings, called from backend/nn/clip.py)
  *   fmx_vae_sample_posterior  DiagonalGaussianDistribution.sample + process_in backend/nn/vae.py:16-29,312-313
  *   fmx_*_bf16             the bfloat16 build of the Flux path's kernels (last section)
+ *   fmx_gguf_dequant_*     GGUF checkpoints: backend/utils.py:27-31 (load_torch_file), backend/operations_gguf.py (dequantize_tensor,
+ *                          quants_mapping), backend/loader.py:181-211 (replace_state_dict), packages_3rdparty/gguf/quants.py (dequantize_blocks)
  */
 #ifndef FMX_H
 #define FMX_H
@@ -488,6 +490,22 @@ int fmx_conv3x3_up2x_bf16(const void* x, int32_t n, int32_t h, int32_t w, int32_
 int fmx_conv3x3_gn_silu_bf16(const fmx_conv_gn_args* args /* host */, int32_t* stats_nchunks /* host, may be null */, void* stream);
 int fmx_vae_sample_posterior_bf16(const void* moments, int32_t ld, const float* noise, int32_t b, int32_t lc, int64_t npix, float scale,
                                   float shift, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * GGUF checkpoints: packed GGML blocks -> the 16-bit resident weights the executors consume, once, at load time (the reference keeps the blocks
+ * packed and dequantises inside every forward: backend/operations_gguf.py dequantize_tensor, packages_3rdparty/gguf/quants.py; its loader
+ * route is backend/utils.py:27-31 and backend/loader.py:181-211).  New symbols only: no existing signature moves, the ABI number stays 11.
+ *   qtype      : the GGML type number as stored in the file.  Supported: F32 0, F16 1, Q4_0 2, Q4_1 3, Q5_0 6, Q5_1 7, Q8_0 8, Q2_K 10, Q3_K 11,
+ *                Q4_K 12, Q5_K 13, Q6_K 14, BF16 30.  Any other number (IQ*, TQ*, Q8_K, ...) returns FMX_E_UNSUPPORTED, the number in fmx_last_error().
+ *   blocks     : n_elements / block_size packed blocks, contiguous, 2-byte aligned (block_size: 32, 256 for the K types, 1 for the float types)
+ *   out        : n_elements fp16 / bf16 values, 16-byte aligned
+ *   n_elements : > 0 and a multiple of block_size
+ * Value contract: what ggml defines in fp32 (the numpy dequantize_blocks of quants.py) rounded ONCE, to nearest even, to the output type -- bit
+ * for bit; values beyond the fp16 range become inf as in numpy / torch.  The reference's torch route computes in the 16-bit type throughout
+ * and rounds several times; DESIGN.md 7 tabulates how far that lies from this contract.
+ * ---------------------------------------------------------------------------------------------- */
+int fmx_gguf_dequant_f16(int32_t qtype, const void* blocks, void* out, int64_t n_elements, void* stream);
+int fmx_gguf_dequant_bf16(int32_t qtype, const void* blocks, void* out, int64_t n_elements, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * HIP-graph helpers: capture everything launched on `stream` between begin/end into an executable graph.

@@ -157,6 +157,9 @@ for _n in ("fmx_gemm_conv_stats", "fmx_groupnorm_stats", "fmx_groupnorm_apply", 
     SIGNATURES[_n + "_bf16"] = SIGNATURES[_n + "_f16"]
 for _n in ("fmx_vae_pack_latent", "fmx_vae_unpack_image", "fmx_vae_sample_posterior"):
     SIGNATURES[_n + "_bf16"] = SIGNATURES[_n]
+# GGUF block dequantisation at load time (qtype, blocks, out, n_elements, stream): new symbols, the ABI number does not move
+for _n in ("fmx_gguf_dequant_f16", "fmx_gguf_dequant_bf16"):
+    SIGNATURES[_n] = [_i32, _vp, _vp, _i64, _vp]
 
 
 def source_tree_hash():

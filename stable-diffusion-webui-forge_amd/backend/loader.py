@@ -27,8 +27,111 @@ def load_torch_file(path, device="cpu"):
     if str(path).endswith((".safetensors", ".sft")):
         from safetensors.torch import load_file
         return load_file(path, device=str(device))
+    if str(path).lower().endswith(".gguf"):      # utils.py:27-31: {name: GGUFTensor} (packed bytes, memory-mapped); dequantize_state_dict expands them
+        from .gguf_file import load_gguf
+        return load_gguf(path)
     sd = torch.load(path, map_location=device, weights_only=True)
     return sd.get("state_dict", sd)
+
+
+def _is_gguf(v):
+    from .gguf_file import GGUFTensor
+    return isinstance(v, GGUFTensor)
+
+
+@torch.inference_mode()
+def dequantize_state_dict(sd, device="cuda", dtype=torch.bfloat16):
+    """Materialise a state dict read from a GGUF file: every GGUFTensor is copied to the device as packed bytes and expanded there into a `dtype`
+    (fp16 / bf16) tensor of its shape by the fmx_gguf_dequant kernels; ordinary tensors pass through untouched.  The reference keeps the blocks and
+    dequantises inside every forward (operations_gguf.py); here the weights become the resident 16-bit tensors the executors consume, once.
+
+    Staging: two pinned host buffers of the largest tensor's packed size, used alternately, and one side stream.  Tensor i+1 is copied into its
+    pinned buffer by the host and sent to the device while tensor i's kernel runs; an event per buffer keeps the host from overwriting bytes whose
+    copy is still in flight.  The packed device copy is freed to the stream-ordered allocator as soon as its kernel is queued, so the extra device
+    memory at any time is a couple of tensors' packed bytes, not the file's."""
+    from .. import hipops
+    if not any(_is_gguf(v) for v in sd.values()):
+        return sd
+    # F32 / F16 / BF16 tensors of the file (norm scales, biases, tables) are ordinary tensors of their own type, as the reference keeps them:
+    # consumers that want fp32 (the T5 bias table) get every stored bit; the executors cast the rest when they bind them
+    plain = {0: torch.float32, 1: torch.float16, 30: torch.bfloat16}
+    sd = {k: (torch.from_numpy(v.data.copy()).view(plain[v.qtype]).reshape(v.shape) if _is_gguf(v) and v.qtype in plain else v) for k, v in sd.items()}
+    todo = [(k, v) for k, v in sd.items() if _is_gguf(v)]
+    if not todo:
+        return sd
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError("GGUF tensors are dequantised on the GPU: device must be a cuda device")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    out = dict(sd)
+    cap = max(v.data.nbytes for _, v in todo)
+    pinned = [torch.empty(cap, dtype=torch.uint8).pin_memory() for _ in range(2)]
+    free = [None, None]                 # event: the buffer's last host-to-device copy has completed
+    with torch.cuda.device(device):
+        stream = torch.cuda.Stream(device)
+        stream.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(stream):
+            for i, (k, v) in enumerate(todo):
+                n = v.data.nbytes
+                slot = i & 1
+                if free[slot] is not None:
+                    free[slot].synchronize()
+                stage = pinned[slot][:n]
+                stage.numpy()[:] = v.data                                   # page-in + copy from the mapping: the file read
+                raw = torch.empty(n, dtype=torch.uint8, device=device)
+                raw.copy_(stage, non_blocking=True)
+                free[slot] = torch.cuda.Event()
+                free[slot].record(stream)
+                out[k] = hipops.gguf_dequant(raw, v.qtype, v.shape, dtype)
+                del raw                                                     # allocated and freed on this stream: reusable by the next tensor
+        torch.cuda.current_stream(device).wait_stream(stream)
+        stream.synchronize()
+    return out
+
+
+# llama.cpp tensor names of a T5 encoder (the GGUF files city96 publishes) -> HF names: the key map of loader.py:185-199, applied the same way
+# (every replacement, in this order, on every key)
+T5_LLAMA_KEY_MAP = (("enc.", "encoder."), (".blk.", ".block."), ("token_embd", "shared"), ("output_norm", "final_layer_norm"),
+                    ("attn_q", "layer.0.SelfAttention.q"), ("attn_k", "layer.0.SelfAttention.k"), ("attn_v", "layer.0.SelfAttention.v"),
+                    ("attn_o", "layer.0.SelfAttention.o"), ("attn_norm", "layer.0.layer_norm"),
+                    ("attn_rel_b", "layer.0.SelfAttention.relative_attention_bias"), ("ffn_up", "layer.1.DenseReluDense.wi_1"),
+                    ("ffn_down", "layer.1.DenseReluDense.wo"), ("ffn_gate", "layer.1.DenseReluDense.wi_0"), ("ffn_norm", "layer.1.layer_norm"))
+T5_PREFIX = "text_encoders.t5xxl.transformer."        # where a Flux checkpoint keeps its text encoders (huggingface_guess' Flux prefixes)
+CLIP_L_PREFIX = "text_encoders.clip_l.transformer."
+
+
+def t5_llama_key(k):
+    for s, d in T5_LLAMA_KEY_MAP:
+        k = k.replace(s, d)
+    return k
+
+
+def replace_state_dict(sd, asd):
+    """loader.py:181-300 for the components that exist on the native path: merge an additional state dict (a VAE, a CLIP-L or a T5 file that comes
+    beside a transformer-only checkpoint) into the checkpoint dict `sd` under the prefix the Flux layout keeps that component at, replacing
+    what was there.  Recognised by the same probe keys as the reference: `decoder.conv_in.weight` (VAE), `enc.blk.0.attn_k.weight` (T5 in
+    llama.cpp naming, renamed first), `encoder.block.0.layer.0.SelfAttention.k.weight` (T5, HF naming),
+    `text_model.encoder.layers.0.layer_norm1.weight` (CLIP-L, 768 wide).  -> sd (modified in place)."""
+    if "enc.blk.0.attn_k.weight" in asd:
+        asd = {t5_llama_key(k): v for k, v in asd.items()}
+
+    def put(prefix, part):
+        for k in [k for k in sd if k.startswith(prefix)]:
+            del sd[k]
+        for k, v in part.items():
+            sd[prefix + k] = v
+
+    if "decoder.conv_in.weight" in asd:
+        put("vae." if flux_prefix(sd) is not None else VAE_PREFIX, asd)
+    elif "encoder.block.0.layer.0.SelfAttention.k.weight" in asd:
+        put(T5_PREFIX, asd)
+    elif "text_model.encoder.layers.0.layer_norm1.weight" in asd and asd["text_model.encoder.layers.0.layer_norm1.weight"].shape[0] == 768:
+        put(CLIP_L_PREFIX, asd)
+    else:
+        raise NotImplementedError("additional state dict not recognised: expected a VAE (decoder.conv_in.weight), a CLIP-L "
+                                  "(text_model.encoder.layers.0.layer_norm1.weight, 768 wide) or a T5 encoder (HF or llama.cpp names)")
+    return sd
 
 
 def preprocess_state_dict(sd):
@@ -144,8 +247,8 @@ FLUX_VAE_PREFIXES = ("vae.", VAE_PREFIX)  # Forge's own Flux checkpoints store t
 
 def split_flux_state_dict(sd):
     """Flux counterpart of split_state_dict: -> ({'transformer', 'vae'}, guess).  The compute type follows the stored tensors as the reference's
-    loader does (bf16 files -> bf16, fp16 files -> fp16; fp32 files run in bf16, the reference's first choice for Flux); quantised storage
-    (fp8 / nf4 / gguf) is outside the native path."""
+    loader does (bf16 files -> bf16, fp16 files -> fp16; fp32 files run in bf16, the reference's first choice for Flux); GGUF files -> bf16);
+    fp8 / nf4 / fp4 storage is outside the native path.  Shapes are all that is read here, so GGUF tensors need no dequantisation yet."""
     prefix = flux_prefix(sd)
     tr = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix) and not k.startswith(FLUX_VAE_PREFIXES + ("text_encoders.",))}
     vae = {}
@@ -155,13 +258,17 @@ def split_flux_state_dict(sd):
         if vae:
             vae = vae_from_diffusers(vae)
             break
-    stored = tr["img_in.weight"].dtype
+    probe = tr["img_in.weight"]
+    # a GGUF file runs in bf16, the reference's first choice for Flux; its tensors are expanded by dequantize_state_dict
+    stored = torch.bfloat16 if _is_gguf(probe) else probe.dtype
     if stored not in (torch.float16, torch.bfloat16, torch.float32):
-        raise NotImplementedError(f"Flux checkpoint stored as {stored}: quantised formats are not on the native path")
+        raise NotImplementedError(f"Flux checkpoint stored as {stored}: fp8 and bitsandbytes nf4 / fp4 storage are not on the native path")
     guess = {"flux_config": detect_flux_config(sd, prefix), "vae_config": detect_vae_config(vae, scaling_factor=0.3611, shift_factor=0.1159) if vae else None, "is_flux": True,
              "dtype": torch.float16 if stored == torch.float16 else torch.bfloat16,
              "ignored": sorted({k.split(".")[0] for k in sd if not k.startswith((prefix,) + FLUX_VAE_PREFIXES)} if prefix else set())}
-    return {"transformer": tr, "vae": vae}, guess
+    # text encoders that ride in the checkpoint dict (additional_state_dicts): handed out as state dicts for IntegratedT5 / IntegratedCLIP
+    encoders = {name: {"transformer." + k[len(p):]: v for k, v in sd.items() if k.startswith(p)} for name, p in (("t5xxl", T5_PREFIX), ("clip_l", CLIP_L_PREFIX))}
+    return {"transformer": tr, "vae": vae, "text_encoders": {n: e for n, e in encoders.items() if e}}, guess
 
 
 def split_state_dict(sd):
@@ -193,15 +300,27 @@ def split_state_dict(sd):
 
 
 @torch.inference_mode()
-def forge_loader(sd, loras=None, device="cuda", prediction_type=None):
+def forge_loader(sd, loras=None, device="cuda", prediction_type=None, additional_state_dicts=None, dtype=None):
     """checkpoint path / state dict (+ optional [(lora_sd, strength)]) -> ForgeDiffusionEngine on the native executors.
-    prediction_type: 'epsilon' | 'v_prediction' | 'edm' to override what the checkpoint's marker keys say (SD2.x-768, v-pred SDXL finetunes)."""
+    prediction_type: 'epsilon' | 'v_prediction' | 'edm' to override what the checkpoint's marker keys say (SD2.x-768, v-pred SDXL finetunes).
+    additional_state_dicts: further files / dicts (VAE, CLIP-L, T5) merged into the checkpoint by replace_state_dict, as the reference's keyword
+    (loader.py:449-452, :498): a Flux GGUF holds the transformer only.  dtype: compute type of a Flux transformer, overriding the stored one.
+    `.gguf` inputs are dequantised on the device (dequantize_state_dict); the text encoders' state dicts are left on the engine as
+    `engine.text_encoder_state_dicts` ({'t5xxl': ..., 'clip_l': ...}, keys as IntegratedT5 / IntegratedCLIP take them)."""
     from .patcher.lora import merge_loras_into_state_dict
     sd = load_torch_file(sd)
+    if additional_state_dicts:
+        sd = dict(sd)
+        for asd in additional_state_dicts:
+            replace_state_dict(sd, load_torch_file(asd))
     if flux_prefix(sd) is not None:
         from .diffusion_engine.base import build_flux_engine
         from .patcher.lora import merge_loras_into_flux_state_dict
         parts, guess = split_flux_state_dict(sd)
+        if dtype is not None:
+            guess["dtype"] = dtype
+        parts["transformer"] = dequantize_state_dict(parts["transformer"], device, guess["dtype"])
+        parts["vae"] = dequantize_state_dict(parts["vae"], device, torch.float16)
         tsd, report = parts["transformer"], None
         if loras:   # native and diffusers-named Flux LoRAs (comfyui_lora_collection/lora.py:286-299, :342-347), merged offline like the UNet's
             tsd, report = merge_loras_into_flux_state_dict(tsd, guess["flux_config"], [(load_torch_file(l), s) for l, s in loras], device=device, dtype=guess["dtype"])
@@ -209,7 +328,11 @@ def forge_loader(sd, loras=None, device="cuda", prediction_type=None):
                                    vae_state_dict=parts["vae"] or None, dtype=guess["dtype"])
         engine.lora_report = report
         engine.model_guess = guess
+        engine.text_encoder_state_dicts = {n: dequantize_state_dict(e, device, guess["dtype"]) for n, e in parts["text_encoders"].items()}
         return engine
+    if any(_is_gguf(v) for v in sd.values()):
+        raise NotImplementedError("GGUF checkpoints are loaded for Flux transformers (and their VAE / text encoder side files); "
+                                  "SD / SDXL UNets in GGUF are not on the native path")
     parts, guess = split_state_dict(sd)
     if prediction_type is not None:
         guess["prediction_type"] = prediction_type

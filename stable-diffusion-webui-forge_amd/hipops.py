@@ -629,6 +629,27 @@ def cast_f16(x, out=None):
     return out
 
 
+def gguf_dequant(raw, qtype, shape, dtype=torch.bfloat16, out=None):
+    """packed GGML blocks (`raw`: a contiguous uint8 device tensor, `qtype`: the GGML type number of the file) -> a `shape`-shaped fp16 / bf16 device
+    tensor: the fp32 value ggml defines, rounded once (include/fmx.h, GGUF section).  Types the kernels do not expand raise FmxError (FMX_E_UNSUPPORTED)."""
+    if not raw.is_cuda or raw.dtype != torch.uint8 or not raw.is_contiguous():
+        raise TypeError("gguf_dequant expects a contiguous uint8 device tensor, got %s on %s" % (raw.dtype, raw.device))
+    sfx = {torch.float16: "_f16", torch.bfloat16: "_bf16"}.get(dtype)
+    if sfx is None:
+        raise TypeError("gguf_dequant produces fp16 or bf16, not %s" % dtype)
+    shape = tuple(int(s) for s in shape)
+    n = 1
+    for s in shape:
+        n *= s
+    from .backend.gguf_file import GGML_TYPES
+    if qtype in GGML_TYPES and n % GGML_TYPES[qtype][1] == 0 and raw.numel() != n // GGML_TYPES[qtype][1] * GGML_TYPES[qtype][2]:
+        raise ValueError("gguf_dequant: %d bytes do not hold %s %s weights" % (raw.numel(), shape, GGML_TYPES[qtype][0]))
+    if out is None:
+        out = empty(shape, dtype, raw.device)
+    _lib.check(getattr(_lib.lib(), "fmx_gguf_dequant" + sfx)(int(qtype), _p(raw), _p(out), n, stream_ptr()), "fmx_gguf_dequant" + sfx)
+    return out
+
+
 def unet_pack_input(x, sigma, reps, sigma_data=1.0, out=None):
     b, c, h, w = x.shape
     if out is None:
