@@ -91,7 +91,12 @@ int fmx_device_info(int* cu_count, int* wave_size, char* arch, int arch_len);
  *               -> (+ residual[row][col])    (gate: the adaLN gates of Flux, backend/nn/flux.py:254-262,301)
  *               stored as fp16 (or fp32 when out_f32 != 0) at out[row*ld_out + col].
  *               act = FMX_ACT_GEGLU: out has nout/2 columns, value*gelu_erf(gate).
- * Requirements: (c0+c1) % 64 == 0, c0 % 64 == 0, all tensors 16-byte aligned, strides % 8 == 0.
+ * Requirements (FMX_E_BADARG otherwise): (c0+c1) % 64 == 0, c0 % 64 == 0; a0, a1, wgt and zero_page 16-byte aligned; a0_stride, a1_stride
+ *               and ldw % 8 == 0.  The alignment of out, bias, rowvec, residual and gate is not enforced and their leading dimensions are
+ *               free (keep the bases 8-byte aligned where the leading dimensions are multiples of 4: 4-wide vector accesses): 16-byte
+ *               bases with ld_out / ld_res / ld_rowvec / ld_gate % 8 == 0, nout % 8 == 0 and fp16 output select the 8-wide epilogue of the
+ *               256-row tiles, leading dimensions % 4 == 0 with nout % 8 == 0 the 4-wide one, anything else (fp32 output included) the
+ *               element-wise one; gate and FMX_ACT_GELU_TANH need at least the 4-wide form.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct fmx_gemm_args {
   const void* a0;

@@ -1,5 +1,5 @@
-"""fp64 references and ulp tolerances shared by the kernel-level parity tests (tests/test_gpu_kernels_bf16.py, tests/test_gpu_small_kernels.py)
-and their CPU companion (tests/test_kernel_ref_teeth.py), which plants one plausible bug into each reference and checks that the GPU tests'
+"""fp64 references and ulp tolerances shared by the kernel-level parity tests (tests/test_gpu_kernels_bf16.py, tests/test_gpu_small_kernels.py,
+tests/test_gpu_gemm_windows.py) and their CPU companion (tests/test_kernel_ref_teeth.py), which plants one plausible bug into each reference and checks that the GPU tests'
 tolerance would reject it.
 
 Discipline: every reference is the same operation in fp64 on the kernel's own rounded inputs (the fp16 / bf16 tensors it read, upcast).
@@ -69,6 +69,20 @@ TEMB_TOL = {torch.bfloat16: (1.0, EPS[torch.bfloat16]), torch.float16: (1.0, EPS
 F32_TOL = (8.0, 2.0 ** -20)
 
 
+# GEMM with a GELU-tanh or GEGLU epilogue, 16-bit output: the activation is one more fp32 function of the fp32 pre-activation before the single
+# rounding.  Its fp32 evaluation (tanh through exp and a reciprocal, erf by a 1.5e-7 polynomial) is wrong by ~1e-7 |x| absolute, four decades
+# under a 16-bit ulp, so CONV_TOL holds unchanged.  Measured on the CPU on the inputs of tests/test_gpu_gemm_windows.py (the same formula in
+# plain fp32 torch on the fp32 pre-activation, against the fp64 reference): worst 0.43x (fp16) / 0.44x (bf16) of CONV_TOL over the GELU-tanh
+# and GEGLU cases -- a rounding, nothing else.  erf-GELU in place of tanh-GELU is NOT resolved at this tolerance (<= ~5e-4 absolute apart).
+GEMM_ACT_TOL = dict(CONV_TOL)
+# GEMM with fp32 output, as (unit per K element, unit per epilogue term).  Products of two 16-bit operands are exact in fp32, so the only errors
+# are fp32 additions: any summation order of K terms is within (K - 1) 2^-24 sum_k |a_k w_k|, and the epilogue (acc * alpha, + bias, + residual:
+# three roundings of partial sums no larger than the summed magnitudes) within 3 * 2^-24 (|alpha| sum|a w| + |bias| + |residual|).  `abs_bound`
+# evaluates  K 2^-24 |alpha| sum|a w|  +  2^-23 (|alpha| sum|a w| + |bias| + |residual| + ...)  per element, which covers both.  Teeth: one
+# dropped K element is ~ sum|a w| / K, thousands of bounds at K = 320; rounding the result through fp16 / bf16 is ~10x / ~80x the bound.
+GEMM_F32_TOL = (2.0 ** -24, 2.0 ** -23)
+
+
 # ---- references -------------------------------------------------------------------------------------------------------------------
 def conv_ref(x, wt, bias=None, *, stride=1, pad=1, pad_rb=None, up=None, rowvec=None, residual=None):
     """x NHWC, wt [co, ci, kh, kw] -> NHWC fp64.  pad_rb = (right, bottom) zero columns / rows only (VAE Downsample: F.pad(x, (0, 1, 0, 1))
@@ -86,6 +100,66 @@ def conv_ref(x, wt, bias=None, *, stride=1, pad=1, pad_rb=None, up=None, rowvec=
     if residual is not None:
         y = y + residual.double().reshape(y.shape)
     return y
+
+
+def excess_abs(got, want, bound):
+    """max |got - want| / bound for a per-element absolute bound (fp64, > 0); a non-finite result is infinitely wrong"""
+    got, want, bound = got.double().cpu(), want.double().cpu(), bound.double().cpu()
+    return float(((got - want).abs() / bound).nan_to_num(nan=math.inf).max())
+
+
+def assert_within_bound(got, want, bound, what):
+    e = excess_abs(got, want, bound)
+    assert e <= 1.0, f"{what}: error {e:.3g}x the derived absolute bound"
+
+
+def gelu_tanh_ref(x):
+    x = x.double()
+    return 0.5 * x * (1.0 + torch.tanh(math.sqrt(2.0 / math.pi) * (x + 0.044715 * x ** 3)))
+
+
+def gelu_erf_ref(x):
+    x = x.double()
+    return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
+
+
+def gemm_ref(a0, w, *, a1=None, alpha=1.0, bias=None, rowvec=None, rows_per_image=None, act="none", gate=None, residual=None):
+    """fmx_gemm_conv as a linear in fp64, the epilogue order of include/fmx.h: acc * alpha (+ bias) (+ rowvec[row // rows_per_image]) -> act ->
+    (* gate[row // rows_per_image]) -> (+ residual).  a0 [M, c0], a1 [M, c1] (channel-concatenated), w [nout, c0 + c1].
+    act: "none", "gelu_tanh", "gelu_erf", or "geglu" on the UN-interleaved weight (rows [value | gate]): value * gelu_erf(gate), nout / 2 columns."""
+    a = a0.double() if a1 is None else torch.cat([a0.double(), a1.double()], -1)
+    m = a.shape[0]
+    per = rows_per_image or m
+    img = torch.arange(m) // per
+    v = (a @ w.double().t()) * alpha
+    if bias is not None:
+        v = v + bias.double()
+    if rowvec is not None:
+        v = v + rowvec.double()[img]
+    if act == "gelu_tanh":
+        v = gelu_tanh_ref(v)
+    elif act == "gelu_erf":
+        v = gelu_erf_ref(v)
+    elif act == "geglu":
+        half = v.shape[1] // 2
+        v = v[:, :half] * gelu_erf_ref(v[:, half:])
+    else:
+        assert act == "none", act
+    if gate is not None:
+        v = v * gate.double()[img]
+    if residual is not None:
+        v = v + residual.double()
+    return v
+
+
+def abs_bound(a0, w, *, a1=None, alpha=1.0, terms=(), tol=GEMM_F32_TOL):
+    """per-element error bound of an fp32-output GEMM (GEMM_F32_TOL): `terms` = the epilogue operands (bias, residual, ...) broadcastable to [M, nout]"""
+    a = a0.double() if a1 is None else torch.cat([a0.double(), a1.double()], -1)
+    mag = (a.abs() @ w.double().abs().t()) * abs(alpha)
+    epi = mag.clone()
+    for t in terms:
+        epi = epi + t.double().abs()
+    return a.shape[1] * tol[0] * mag + tol[1] * epi
 
 
 def groupnorm_ref(x, gamma, beta, eps, groups=32, silu=False):

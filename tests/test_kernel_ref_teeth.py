@@ -1,5 +1,5 @@
-"""CPU: the kernel-level GPU tests have teeth.  For each test in tests/test_gpu_kernels_bf16.py, tests/test_gpu_small_kernels.py and each test
-family of tests/test_gpu_attention_generic.py, one
+"""CPU: the kernel-level GPU tests have teeth.  For each test in tests/test_gpu_kernels_bf16.py, tests/test_gpu_small_kernels.py, each test
+family of tests/test_gpu_attention_generic.py and each window case of tests/test_gpu_gemm_windows.py, one
 plausible subtle bug is planted into the fp64 reference (tests/kernel_refs.py) and evaluated on that test's own inputs; the planted result must
 lie outside the GPU test's tolerance by at least 4x (kernel_refs.excess >= 4), or -- for the exact tests -- differ in at least 4 places.
 Runs without a GPU, so a tolerance too loose to catch anything fails before anyone gets a GPU."""
@@ -11,6 +11,7 @@ import torch.nn.functional as F
 
 import kernel_refs as R
 import test_gpu_attention_generic as G
+import test_gpu_gemm_windows as W
 import test_gpu_kernels_bf16 as B
 import test_gpu_small_kernels as S
 
@@ -326,3 +327,177 @@ def test_mask_pad_columns_added_is_caught():
     leaked = mask.double().clone()
     leaked[..., nk:] = -math.inf + leaked[..., nk:]
     bites(G.reference(q, k, v, nkp, d, mask=leaked, dev="cpu"), want, H16, R.ATTN_TOL[H16], "mask pad columns added")
+
+
+# ---- GEMM window file -------------------------------------------------------------------------------------------------------------------
+DTS = [H16, BF]
+
+
+def _one(case_id, dtype):
+    """(case, its single launch, its fp64 reference)"""
+    case = W.build(case_id, dtype)
+    return case, case.launches[0], W.case_refs(case_id, dtype)[0]
+
+
+def _strided_read(win, rows, cols, ld):
+    """the [rows, cols] elements a kernel reads from win's buffer when it steps `ld` elements per row from the window's first element"""
+    idx = win.values.storage_offset() + torch.arange(rows)[:, None] * ld + torch.arange(cols)[None]
+    return win.buf.reshape(-1)[idx]
+
+
+def _pre(L, img_rows=None):
+    """fp64 pre-activation acc * alpha + bias + rowvec[image] of a linear launch"""
+    return R.gemm_ref(L.a0.values, L.w.values, a1=None if L.a1 is None else L.a1.values, alpha=L.alpha, bias=None if L.bias is None else L.bias.values,
+                      rowvec=None if L.rowvec is None else L.rowvec.values, rows_per_image=img_rows or L.per)
+
+
+def test_every_window_case_runs_on_each_tile_family():
+    """condition of the GPU file: besides the dispatcher's own refusals nothing is skipped, so every case runs on a 2-stage 4-wave tile, a ring
+    tile and -- where every launch is eligible8 -- a 256-row tile; and the operands keep the contract (16-byte bases, A / W strides % 8)"""
+    for case_id in W.CASE_IDS:
+        for dtype in DTS:
+            case = W.build(case_id, dtype)
+            runs = lambda t: all(W.refusal(L, case.out_buf, t) is None for L in case.launches)  # noqa: E731
+            assert runs(0) and any(runs(t) for t in W.TWO_STAGE) and any(runs(t) for t in W.RING), case_id
+            if all(W.eligible8(L, case.out_buf) for L in case.launches):
+                assert any(runs(t) for t in W.ROWS256), case_id
+            for L in case.launches:
+                for win in (L.a0, L.a1, L.w, L.bias, L.rowvec, L.gate, L.residual):
+                    if win is not None:
+                        assert (win.values.storage_offset() * 2) % 16 == 0, case_id
+                for win in (L.a0, L.a1, L.w):
+                    assert win is None or win.values.stride(0) % 8 == 0, case_id
+                out = case.out_buf[L.rows, L.cols]
+                assert (out.storage_offset() * out.element_size()) % 16 == 0, case_id
+    assert any(all(W.eligible8(L, W.build(c, H16).out_buf) for L in W.build(c, H16).launches) for c in W.CASE_IDS if c.startswith("out_cols_eligible8"))
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_window_residual_addressed_with_ld_out_is_caught(dtype):
+    """residual_window: the residual read `ld_out` instead of `ld_res` elements per row (neighbouring columns of the residual's buffer)"""
+    for case_id in ("residual_window-0", "residual_window-2"):
+        case, L, want = _one(case_id, dtype)
+        wrong = _strided_read(L.residual, L.m, L.ncols, case.out_buf.stride(0))
+        bites(want - L.residual.values.double() + wrong.double(), want, dtype, W.tolerance(L, dtype), case_id)
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_window_image_index_from_the_tile_height_is_caught(dtype):
+    """rowvec_gate_strided, two_source_full_epilogue: rowvec / gate image index row // roundup(per_img, 128) -- right for tile-aligned images"""
+    for case_id in ("rowvec_gate_strided-0", "rowvec_gate_strided-1", "two_source_full_epilogue-0"):
+        case, L, want = _one(case_id, dtype)
+        img = (torch.arange(L.m) // (-(-L.per // 128) * 128)).clamp(max=L.n_img - 1)
+        v = _pre(L) - (0 if L.rowvec is None else L.rowvec.values.double()[torch.arange(L.m) // L.per] - L.rowvec.values.double()[img])
+        v = R.gelu_tanh_ref(v) if L.act == "gelu_tanh" else v
+        v = v * L.gate.values.double()[img]
+        if L.inplace:
+            v = v + case.out_buf[L.rows, L.cols].double()
+        bites(v, want, dtype, W.tolerance(L, dtype), case_id)
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_window_alpha_applied_to_the_bias_is_caught(dtype):
+    """alpha_order: (acc + bias) * alpha instead of acc * alpha + bias"""
+    for case_id in ("alpha_order-0", "alpha_order-1"):
+        _, L, want = _one(case_id, dtype)
+        bites(want + (L.alpha - 1.0) * L.bias.values.double(), want, dtype, W.tolerance(L, dtype), case_id)
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_window_a_read_from_the_wrong_place_is_caught(dtype):
+    """a_windows: A read from column 0 of its buffer instead of the window's offset; the second source stepped with the first source's stride"""
+    _, L, want = _one("a_windows-0", dtype)
+    rows = L.a0.idx[0]
+    col0 = L.a0.buf[rows, :L.a0.values.shape[1]]
+    bites(R.gemm_ref(col0, L.w.values, bias=L.bias.values), want, dtype, W.tolerance(L, dtype), "a_windows-0: A from column 0")
+    _, L, want = _one("a_windows-2", dtype)
+    a1 = _strided_read(L.a1, L.m, L.a1.values.shape[1], L.a0.values.stride(0))
+    bites(R.gemm_ref(L.a0.values, L.w.values, a1=a1, bias=L.bias.values), want, dtype, W.tolerance(L, dtype), "a_windows-2: a1 with a0's stride")
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_window_ldw_ignored_is_caught(dtype):
+    """w_window: weight rows taken K elements apart instead of ldw"""
+    _, L, want = _one("w_window-0", dtype)
+    k = L.w.values.shape[1]
+    bites(R.gemm_ref(L.a0.values, _strided_read(L.w, L.nout, k, k), bias=L.bias.values), want, dtype, W.tolerance(L, dtype), "w_window-0: ldw ignored")
+
+
+@pytest.mark.parametrize("case_id", ["out_cols_ragged-0", "out_cols_ragged-1"])
+def test_window_last_partial_group_stored_in_full_trips_the_sentinel_rule(case_id):
+    """out_cols_ragged (t = 77, 33): the last partial group of 4 columns stored as a full group writes 4 - nout % 4 pad columns of every row; the
+    sentinel rule must see at least 4 changed elements.  (With the dense odd rows of out_ld_odd the same overrun lands in the head of the NEXT
+    row, inside the window, and only the last row's 2-3 elements reach the sentinel: that case relies on the value comparison.)"""
+    case = W.build(case_id, H16)
+    L, want = case.launches[0], W.case_refs(case_id, H16)[0]
+    after = case.out_buf.clone()
+    flat, ld = after.reshape(-1), after.stride(0)
+    full = -(-L.ncols // 4) * 4
+    vals = torch.zeros(L.m, full, dtype=H16)
+    vals[:, :L.ncols] = want.to(H16)
+    idx = after[L.rows, L.cols].storage_offset() + torch.arange(L.m)[:, None] * ld + torch.arange(full)[None]
+    flat[idx] = vals
+    assert full > L.ncols and W.changed_outside(case.out_buf, after, L.rows, L.cols) >= TEETH
+    clean = case.out_buf.clone()
+    clean[L.rows, L.cols] = want.to(H16)
+    assert W.changed_outside(case.out_buf, clean, L.rows, L.cols) == 0
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_window_geglu_halves_swapped_is_caught(dtype):
+    """geglu_window: gelu(value) * gate for value * gelu(gate)"""
+    for case_id in ("geglu_window-0", "geglu_window-1"):
+        _, L, want = _one(case_id, dtype)
+        h = _pre(L)
+        planted = R.gelu_erf_ref(h[:, :L.ncols]) * h[:, L.ncols:] + (0 if L.residual is None else L.residual.values.double())
+        bites(planted, want, dtype, W.tolerance(L, dtype), case_id)
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_window_out_cols_eligible8_row_stride_from_nout_is_caught(dtype):
+    """out_cols_eligible8 (sentinel rule): rows stored nout instead of ld_out elements apart run through the left and right surroundings"""
+    case, L, want = _one("out_cols_eligible8-0", dtype)
+    after = case.out_buf.clone()
+    idx = after[L.rows, L.cols].storage_offset() + torch.arange(L.m)[:, None] * L.nout + torch.arange(L.nout)[None]
+    after.reshape(-1)[idx] = want.to(dtype)
+    assert W.changed_outside(case.out_buf, after, L.rows, L.cols) >= TEETH
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_fp32_output_rounded_through_the_16_bit_type_is_caught(dtype):
+    """fp32_out: the result rounded to fp16 / bf16 before the fp32 store must exceed GEMM_F32_TOL by 4x; a plain fp32 evaluation stays inside"""
+    for i in (0, 1):
+        L = W.build_f32(i, dtype).launches[0]
+        want, bound = W.f32_ref_and_bound(L)
+        e = R.excess_abs(want.to(dtype), want, bound)
+        assert e >= TEETH, f"fp32_out {W.F32_CASES[i]}: rounding through {dtype} is only {e:.3g}x the bound"
+        plain = (L.a0.values.float() @ L.w.values.float().t()) * L.alpha + L.bias.values.float() + L.residual.values.float()
+        assert R.excess_abs(plain, want, bound) <= 0.25
+        dropped = want - L.alpha * L.a0.values.double()[:, -1:] * L.w.values.double()[:, -1][None]
+        assert R.excess_abs(dropped, want, bound) >= 100 * TEETH
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_gate_before_the_activation_is_caught_and_plain_fp32_meets_the_tolerance(dtype):
+    """rowvec_gate_strided with GELU-tanh: gelu(pre * gate) for gelu(pre) * gate; and the same formulas in plain fp32 torch on the fp32
+    pre-activation, rounded once, lie inside GEMM_ACT_TOL (the figure quoted at kernel_refs.GEMM_ACT_TOL)"""
+    worst = 0.0
+    for case_id in ("rowvec_gate_strided-1", "rowvec_gate_strided-3", "rowvec_gate_strided-4", "geglu_window-0", "geglu_window-1"):
+        _, L, want = _one(case_id, dtype)
+        img = torch.arange(L.m) // L.per
+        if L.gate is not None:
+            bites(R.gelu_tanh_ref(_pre(L) * L.gate.values.double()[img]), want, dtype, W.tolerance(L, dtype), case_id)
+        pre = L.a0.values.float() @ L.w.values.float().t()
+        if L.bias is not None:
+            pre = pre + L.bias.values.float()
+        if L.rowvec is not None:
+            pre = pre + L.rowvec.values.float()[img]
+        if L.act == "geglu":
+            v = pre[:, :L.ncols] * F.gelu(pre[:, L.ncols:])
+        else:
+            v = F.gelu(pre, approximate="tanh") * L.gate.values.float()[img]
+        if L.residual is not None:
+            v = v + L.residual.values.float()
+        worst = max(worst, R.excess(v.to(dtype), want, dtype, *R.CONV_TOL[dtype]))
+    print(f"plain fp32 activation epilogues, {dtype}: worst {worst:.3g}x CONV_TOL")
+    assert worst <= 1.0 and R.GEMM_ACT_TOL[dtype] == R.CONV_TOL[dtype]
