@@ -226,7 +226,8 @@ int fmx_attention_f16(const fmx_attn_args* args /* host */, void* stream);
 
 /* Fused attention of ONE head of width 512 (the VAE mid-block attention: backend/nn/vae.py:118-137 -> attention.py:412-422), N up to 16 384
  * tokens, without materialising the scores: O = softmax(Q K^T * scale) V, the head dimension split across the waves of a workgroup.
- *   q, k : fp16 token-major, token i of image b at q[b*q_bs + i*q_rs + c], c < 512 (q and k may be the two halves of one [B*N][1024] buffer)
+ *   q, k : fp16 token-major, token i of image b at q[b*q_bs + i*q_rs + c], c < 512 (q and k may be the two halves of one [B*N][1024] buffer);
+ *          q rows >= nq and k rows >= nk of an image are never read and may hold anything, non-finite values included
  *   vt   : fp16 V TRANSPOSED, (b, c, j) at vt[b*vt_bs + c*vt_ds + j]; every row holds nk_pad keys (multiple of 32), keys >= nk must be finite (zeros)
  *   o    : fp16 token-major like q.   16-byte aligned bases, strides % 8 == 0, an image's K / V^T spans < 2 GB. */
 int fmx_attention_single_head512_f16(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* vt,
@@ -372,7 +373,9 @@ int fmx_im2col3x3_smallc(const void* x, int32_t ldx, int32_t n, int32_t c, int32
 /* 3x3 convolution (stride 1, zero padding 1) with at most 4 output channels: the VAE decoder's conv_out (/root/reference/backend/nn/vae.py:248-271, the
  * last layer: 128 -> 3 channels at the full image size) and the UNet's `out` convolution (backend/nn/unet.py:760-764: 320 -> 4).  x NHWC [n][h][w][c] 16-bit,
  * c a multiple of 32 (walked in channel chunks of 128 / 64 / 32); wgt [nout][ky][kx][c] (the GEMM entry's
- * weight layout); bias [nout] or null; out [n*h*w][ld_out], columns >= nout of an ld_out = 4 output are written as zeros.  A direct kernel (the input
+ * weight layout); bias [nout] or null; out [n*h*w][ld_out], columns >= nout of an ld_out = 4 output are written as zeros (one 8-byte store per pixel:
+ * out 8-byte aligned); with ld_out > 4 exactly the nout columns of a pixel are written and columns [nout, ld_out) stay untouched (out may be a column window
+ * of a wider buffer at any element offset).  A direct kernel (the input
  * patch of a 4 x 32 pixel tile staged once in LDS) instead of the implicit GEMM's nine-fold im2col gather; HBM-bound (ABI 8). */
 int fmx_conv3x3_narrow_f16(const void* x, int32_t n, int32_t h, int32_t w, int32_t c, const void* wgt, const void* bias, int32_t nout, void* out,
                            int32_t ld_out, void* stream);

@@ -819,16 +819,22 @@ _UP2X = _lib.knob("FMX_UP2X", "1") != "0"
 def fold_up2x_weights(wk, c):
     """[nout, 9 * c] (the GEMM layout: taps (ky, kx) row-major, then channels) -> [4, nout, 4 * c]: the tap sums of the four parity phases of
     conv3x3(nearest_upsample_x2(x)) -- phase 2 * py + px, its 2 x 2 taps (dy, dx) row-major (include/fmx.h fmx_conv3x3_up2x).  Even output rows
-    see input rows {iy - 1, iy} through {w[0], w[1] + w[2]}, odd ones {iy, iy + 1} through {w[0] + w[1], w[2]}; columns alike.  Summed in fp32,
-    rounded ONCE to the element type."""
+    see input rows {iy - 1, iy} through {w[0], w[1] + w[2]}, odd ones {iy, iy + 1} through {w[0] + w[1], w[2]}; columns alike.  Summed in fp64
+    (exact for up to four 16-bit summands within ~40 binades of each other), rounded ONCE to the element type: through fp32 with round-to-odd, so
+    that the second rounding sees on which side of a tie the sum lies (an fp32 sum, or torch's double -> fp32 -> 16-bit cast, rounds sums next to a
+    tie twice).  Weights of one magnitude, as layers have them, give the bits the fp32 sum gave."""
     nout = wk.shape[0]
-    w = wk.reshape(nout, 3, 3, c).float()
+    w = wk.reshape(nout, 3, 3, c).double()
 
     def fold(t, dim, parity):
         a, b, d = t.unbind(dim)
         return torch.stack([a, b + d] if parity == 0 else [a + b, d], dim)
-    phases = [fold(fold(w, 1, py), 2, px).reshape(nout, 4 * c) for py in (0, 1) for px in (0, 1)]
-    return torch.stack(phases).to(wk.dtype).contiguous()
+    s = torch.stack([fold(fold(w, 1, py), 2, px).reshape(nout, 4 * c) for py in (0, 1) for px in (0, 1)])
+    f = s.float()
+    inexact = f.double() != s
+    toward_zero = torch.where(f.double().abs() > s.abs(), torch.nextafter(f, torch.zeros_like(f)), f)      # the fp32 neighbour below |s|
+    f = torch.where(inexact, (toward_zero.view(torch.int32) | 1).view(torch.float32), f)                  # ... with the sticky bit set
+    return f.to(wk.dtype).contiguous()
 
 
 def conv3x3_up2x_supported(x, nout, out_hw=None):

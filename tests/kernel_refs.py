@@ -1,5 +1,5 @@
 """fp64 references and ulp tolerances shared by the kernel-level parity tests (tests/test_gpu_kernels_bf16.py, tests/test_gpu_small_kernels.py,
-tests/test_gpu_gemm_windows.py) and their CPU companion (tests/test_kernel_ref_teeth.py), which plants one plausible bug into each reference and checks that the GPU tests'
+tests/test_gpu_gemm_windows.py, tests/test_gpu_vae_direct.py) and their CPU companion (tests/test_kernel_ref_teeth.py), which plants one plausible bug into each reference and checks that the GPU tests'
 tolerance would reject it.
 
 Discipline: every reference is the same operation in fp64 on the kernel's own rounded inputs (the fp16 / bf16 tensors it read, upcast).
@@ -81,6 +81,15 @@ GEMM_ACT_TOL = dict(CONV_TOL)
 # evaluates  K 2^-24 |alpha| sum|a w|  +  2^-23 (|alpha| sum|a w| + |bias| + |residual| + ...)  per element, which covers both.  Teeth: one
 # dropped K element is ~ sum|a w| / K, thousands of bounds at K = 320; rounding the result through fp16 / bf16 is ~10x / ~80x the bound.
 GEMM_F32_TOL = (2.0 ** -24, 2.0 ** -23)
+
+# The VAE decoder's direct kernels (tests/test_gpu_vae_direct.py) are held to CONV_TOL / ATTN_TOL as they stand.  For the GroupNorm-fused
+# convolutions the normalised activation is a rounding site that reference and kernel share (gn_silu_conv_ref rounds it once); an activation that
+# the kernel's fp32 scale / shift puts on the other neighbour moves an output by |w| ulp(act), with |w| ~ 1 / sqrt(9 cin) <= 0.042: under 1/20 of
+# CONV_TOL's floor per flipped activation.  Worst excess of the CPU emulations (gn_silu_conv_emul / attn512_emul below and plain fp32 convolutions:
+# the kernels' arithmetic in fp32 torch) over every case of that file, fp16 / bf16, in units of the tolerance:
+#   conv3x3_gn_silu 0.41 / 0.40, conv3x3_narrow 0.33 / 0.33, conv3x3_narrow_gn_silu 0.34 / 0.34, conv3x3_up2x 0.47 / 0.47, attention512 0.21 / 0.21
+# (tests/test_kernel_ref_teeth.py asserts <= 1 for each and prints them).  The GPU tests print their own excess per case (`MEASURED ...`, pytest -s);
+# no MI355X figures are recorded here yet.
 
 
 # ---- references -------------------------------------------------------------------------------------------------------------------
@@ -297,3 +306,119 @@ def strided_ref(src, dims, src_strides, dst_dtype):
     if v.dtype == torch.bool:
         v = torch.where(v, torch.tensor(0.0), torch.tensor(-math.inf))
     return v.float().to(dst_dtype)
+
+
+# ---- the VAE decoder's direct kernels (tests/test_gpu_vae_direct.py) -----------------------------------------------------------------------
+def gn_silu_conv_ref(x, gamma, beta, eps, wt, bias, residual, dtype, groups=32):
+    """fmx_conv3x3_gn_silu / fmx_conv3x3_narrow_gn_silu: fp64 GroupNorm + SiLU of x (NHWC), rounded ONCE to `dtype` (the staged patch holds the tensor
+    groupnorm() would store: the kernel's own rounding site), zero padding of THAT tensor, fp64 3x3 convolution with wt [co, ci, 3, 3] + bias + residual"""
+    act = rounded(groupnorm_ref(x, gamma, beta, eps, groups=groups, silu=True), dtype)
+    return conv_ref(act, wt, bias, pad=1, residual=residual)
+
+
+def up2x_ref(x, w4, bias):
+    """fmx_conv3x3_up2x: the four 2 x 2 phase convolutions in fp64 on the rounded tap sums w4 [4, nout, 2 * 2 * c] the kernel receives (phase 2 py + px,
+    taps (dy, dx) row-major): even output rows / columns see inputs {i - 1, i}, odd ones {i, i + 1}.  x NHWC -> [n, 2h, 2w, nout] fp64"""
+    n, h, w, c = x.shape
+    nout = w4.shape[1]
+    xin = x.double().permute(0, 3, 1, 2)
+    out = torch.zeros(n, nout, 2 * h, 2 * w, dtype=torch.float64)
+    for ph in range(4):
+        py, px = ph >> 1, ph & 1
+        wp = w4[ph].double().view(nout, 2, 2, c).permute(0, 3, 1, 2)
+        out[:, :, py::2, px::2] = F.conv2d(F.pad(xin, (1 - px, px, 1 - py, py)), wp, None if bias is None else bias.double())
+    return out.permute(0, 2, 3, 1)
+
+
+_UP2X_TAPS = {0: ((0,), (1, 2)), 1: ((0, 1), (2,))}     # parity -> the 3-tap indices summed into 2-tap slot 0 / 1
+
+
+def fold_up2x_ref(wk, c):
+    """fp64 tap sums of a [nout, 9 * c] weight (taps (ky, kx) row-major, then channels) -> [4, nout, 4 * c], written out index by index"""
+    nout = wk.shape[0]
+    w = wk.double().reshape(nout, 3, 3, c)
+    out = torch.zeros(4, nout, 2, 2, c, dtype=torch.float64)
+    for py in (0, 1):
+        for px in (0, 1):
+            for dy in (0, 1):
+                for dx in (0, 1):
+                    for ky in _UP2X_TAPS[py][dy]:
+                        for kx in _UP2X_TAPS[px][dx]:
+                            out[2 * py + px, :, dy, dx] += w[:, ky, kx]
+    return out.reshape(4, nout, 4 * c)
+
+
+def round_to(want, dtype):
+    """fp64 values rounded to nearest-even in `dtype`, evaluated in fp64 (no intermediate fp32 rounding) -> (rounded fp64, distance of `want` from the
+    nearest rounding tie relative to |want|; inf at 0)"""
+    u = ulp(want, dtype)
+    t = want.double() / u
+    tie = ((t - torch.floor(t)) - 0.5).abs() * u / want.double().abs().clamp_min(1e-300)
+    return torch.round(t) * u, torch.where(want == 0, torch.full_like(tie, math.inf), tie)
+
+
+def gn_fold_emul(x, gamma, beta, eps, groups=32):
+    """the {scale, shift} table as csrc/fmx_norm.hip folds it: fp32 per-channel {sum, sum of squares}, mean and variance of a group in double, mean and
+    rstd in fp32, scale = rstd * gamma, shift = beta - mean * scale in fp32.  x NHWC -> (scale, shift) fp32 [n, c]"""
+    n, c = x.shape[0], x.shape[-1]
+    xf = x.float().reshape(n, -1, c)
+    cnt = float(xf.shape[1] * (c // groups))
+    s = xf.sum(1).double().view(n, groups, -1).sum(-1) / cnt
+    q = (xf * xf).sum(1).double().view(n, groups, -1).sum(-1) / cnt
+    mean = s.float()
+    rstd = torch.rsqrt((q - s * s).clamp_min(0.0).float() + eps)
+    sc = rstd.repeat_interleave(c // groups, 1) * gamma.float()
+    return sc, beta.float() - mean.repeat_interleave(c // groups, 1) * sc
+
+
+def gn_silu_conv_emul(x, gamma, beta, eps, wt, bias, residual, dtype, groups=32, plant=None):
+    """the fused kernels' arithmetic in fp32 torch: table from gn_fold_emul, one multiply-add + SiLU in fp32, rounded to `dtype`, zeros outside the image,
+    fp32 convolution + bias + residual, one rounding.  plant: None, or one bug -- "pad_before_norm" (the halo holds silu(shift[c]): x padded before the
+    norm), "table_of_image0", "table_one_chunk_on" (channels c use the table of c + 64), "kykx" (taps transposed)."""
+    n, h, w, c = x.shape
+    sc, sh = gn_fold_emul(x, gamma, beta, eps, groups)
+    if plant == "table_of_image0":
+        sc, sh = sc[:1].expand(n, c), sh[:1].expand(n, c)
+    if plant == "table_one_chunk_on":
+        idx = (torch.arange(c) + 64) % c
+        sc, sh = sc[:, idx], sh[:, idx]
+    silu = lambda y: y * torch.sigmoid(y)  # noqa: E731
+    act = silu(x.float() * sc[:, None, None, :] + sh[:, None, None, :]).to(dtype).float().permute(0, 3, 1, 2)
+    act = F.pad(act, (1, 1, 1, 1))
+    if plant == "pad_before_norm":
+        halo = silu(sh).to(dtype).float()[:, :, None, None].expand(n, c, h + 2, w + 2).clone()
+        halo[:, :, 1:-1, 1:-1] = act[:, :, 1:-1, 1:-1]
+        act = halo
+    wf = wt.float().transpose(2, 3) if plant == "kykx" else wt.float()
+    y = F.conv2d(act, wf, None if bias is None else bias.float()).permute(0, 2, 3, 1)
+    if residual is not None:
+        y = y + residual.float().reshape(y.shape)
+    return y.to(dtype)
+
+
+def attn512_emul(q, k, v, nk, scale, dtype, plant=None):
+    """fmx_attention_single_head512 in fp32 torch: Q pre-scaled by scale * log2(e) and rounded to `dtype`, an online softmax in the log2 domain over 32-key
+    steps, P rounded to `dtype` before P V, one rounding of O.  q [b, nq, 512]; k, v [b, >= nk, 512] INCLUDING whatever the buffers hold behind key nk.
+    plant: None, "pad_keys_attend" (keys >= nk of the last step not masked), "no_rescale" (the accumulator keeps its scale when the maximum rises)"""
+    b, nq, c = q.shape
+    steps = -(-nk // 32)
+    pad = steps * 32 - k.shape[1]
+    if pad > 0:
+        k, v = F.pad(k, (0, 0, 0, pad)), F.pad(v, (0, 0, 0, pad))
+    qs = (q.float() * (scale * 1.44269504088896340736)).to(dtype).float()
+    m = torch.full((b, nq), -math.inf)
+    l, o = torch.zeros(b, nq), torch.zeros(b, nq, c)
+    for kt in range(steps):
+        sl = slice(kt * 32, kt * 32 + 32)
+        s = qs @ k[:, sl].float().transpose(1, 2)
+        if plant != "pad_keys_attend":
+            s[:, :, max(0, nk - kt * 32):] = -math.inf
+        m_new = torch.maximum(m, s.max(-1).values)
+        alpha = torch.exp2(m - m_new)
+        p = torch.exp2(s - m_new[..., None])
+        l = l * alpha + p.sum(-1)
+        if plant != "no_rescale":
+            o = o * alpha[..., None]
+        o = o + p.to(dtype).float() @ v[:, sl].float()
+        m = m_new
+    return (o / l[..., None]).to(dtype)

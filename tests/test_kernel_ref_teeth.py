@@ -1,5 +1,5 @@
 """CPU: the kernel-level GPU tests have teeth.  For each test in tests/test_gpu_kernels_bf16.py, tests/test_gpu_small_kernels.py, each test
-family of tests/test_gpu_attention_generic.py and each window case of tests/test_gpu_gemm_windows.py, one
+family of tests/test_gpu_attention_generic.py, each window case of tests/test_gpu_gemm_windows.py and each check of tests/test_gpu_vae_direct.py, one
 plausible subtle bug is planted into the fp64 reference (tests/kernel_refs.py) and evaluated on that test's own inputs; the planted result must
 lie outside the GPU test's tolerance by at least 4x (kernel_refs.excess >= 4), or -- for the exact tests -- differ in at least 4 places.
 Runs without a GPU, so a tolerance too loose to catch anything fails before anyone gets a GPU."""
@@ -14,6 +14,7 @@ import test_gpu_attention_generic as G
 import test_gpu_gemm_windows as W
 import test_gpu_kernels_bf16 as B
 import test_gpu_small_kernels as S
+import test_gpu_vae_direct as V
 
 BF, H16 = torch.bfloat16, torch.float16
 TEETH = 4.0
@@ -501,3 +502,192 @@ def test_gate_before_the_activation_is_caught_and_plain_fp32_meets_the_tolerance
         worst = max(worst, R.excess(v.to(dtype), want, dtype, *R.CONV_TOL[dtype]))
     print(f"plain fp32 activation epilogues, {dtype}: worst {worst:.3g}x CONV_TOL")
     assert worst <= 1.0 and R.GEMM_ACT_TOL[dtype] == R.CONV_TOL[dtype]
+
+
+# ---- the VAE decoder's direct kernels (tests/test_gpu_vae_direct.py) --------------------------------------------------------------------------
+# Every planted bug goes into the fp32 emulation of the kernel's arithmetic (kernel_refs.gn_silu_conv_emul / attn512_emul, plain fp32 convolutions)
+# and is judged against the GPU test's fp64 reference at the GPU test's tolerance; the unplanted emulation has to stay inside it.
+WORST = {}     # kernel -> worst unplanted excess seen (printed by test_zz_report_worst_emulation_excess; the figures beside kernel_refs.CONV_TOL)
+
+
+def _inside(got, want, dtype, tol, kernel, what):
+    e = R.excess(got, want, dtype, *tol)
+    WORST[(kernel, dtype)] = max(WORST.get((kernel, dtype), 0.0), e)
+    assert e <= 1.0, f"{what}: the unplanted emulation is {e:.3g}x the tolerance"
+
+
+def _gn_emul(k, dtype, residual, plant=None):
+    return R.gn_silu_conv_emul(k.x, k.gamma, k.beta, V.EPS_GN, k.wt, k.bias, k.res if residual else None, dtype, groups=k.groups, plant=plant).reshape(k.m, k.nout)
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_vae_gn_silu_emulation_meets_the_tolerance_on_every_case(dtype):
+    for shape in V.GN_SHAPES:
+        for residual in (False, True):
+            _inside(_gn_emul(V.gn_case(shape, dtype), dtype, residual), V.gn_ref(shape, dtype, residual=residual), dtype, R.CONV_TOL[dtype], "conv3x3_gn_silu", shape)
+    k = V.gn_case((2, 8, 32, 128), dtype, groups=16)
+    _inside(_gn_emul(k, dtype, True), V.gn_ref((2, 8, 32, 128), dtype, 16, residual=True), dtype, R.CONV_TOL[dtype], "conv3x3_gn_silu", "16 groups")
+    for shape in V.NARROW_SHAPES:
+        k = V.gn_case(shape[:4], dtype, 32, shape[4])
+        _inside(_gn_emul(k, dtype, False), V.gn_ref(shape[:4], dtype, 32, shape[4]), dtype, R.CONV_TOL[dtype], "conv3x3_narrow_gn_silu", shape)
+        k = V.narrow_case(shape, dtype)
+        got = F.conv2d(k.x.float().permute(0, 3, 1, 2), k.wt.float(), k.bias.float(), padding=1).permute(0, 2, 3, 1).reshape(k.m, k.nout).to(dtype)
+        _inside(got, V.narrow_ref(shape, dtype), dtype, R.CONV_TOL[dtype], "conv3x3_narrow", shape)
+
+
+@pytest.mark.parametrize("dtype", DTS)
+@pytest.mark.parametrize("plant", ["pad_before_norm", "table_of_image0", "table_one_chunk_on", "kykx"])
+def test_vae_gn_silu_planted_bugs_are_caught(plant, dtype):
+    """the halo padded before the norm; image 0's {scale, shift} for every image; the table of channels c + 64; ky / kx transposed -- on a case with several
+    images and chunks for the wide kernel, and on a narrow one"""
+    shape = (3, 9, 33, 64) if plant in ("pad_before_norm", "kykx") else (2, 17, 65, 192)
+    bites(_gn_emul(V.gn_case(shape, dtype), dtype, True, plant), V.gn_ref(shape, dtype, residual=True), dtype, R.CONV_TOL[dtype], f"gn_silu {plant}")
+    nshape = (3, 5, 33, 96, 4) if plant != "table_one_chunk_on" else (2, 6, 31, 320, 4)
+    k = V.gn_case(nshape[:4], dtype, 32, nshape[4])
+    bites(_gn_emul(k, dtype, False, plant), V.gn_ref(nshape[:4], dtype, 32, nshape[4]), dtype, R.CONV_TOL[dtype], f"narrow gn_silu {plant}")
+    kn = V.narrow_case(nshape, dtype)
+    if plant == "kykx":
+        got = F.conv2d(kn.x.float().permute(0, 3, 1, 2), kn.wt.float().transpose(2, 3), kn.bias.float(), padding=1).permute(0, 2, 3, 1).reshape(kn.m, kn.nout)
+        bites(got.to(dtype), V.narrow_ref(nshape, dtype), dtype, R.CONV_TOL[dtype], "narrow kykx")
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_vae_gn_silu_residual_addressed_with_ld_out_is_caught(dtype):
+    """the residual window (ld_res 136) stepped through with ld_out = 160"""
+    for shape in ((2, 8, 32, 128), (3, 9, 33, 64)):
+        k = V.gn_case(shape, dtype)
+        _, _, _, res = V.gn_destination(k, "residual_windows", dtype)
+        idx = res.values.storage_offset() + torch.arange(k.m)[:, None] * 160 + torch.arange(V.COUT)[None]
+        wrong = res.buf.reshape(-1)[idx % res.buf.numel()]
+        want = V.gn_ref(shape, dtype, residual=True)
+        bites(_gn_emul(k, dtype, False).double() + wrong.double(), want, dtype, R.CONV_TOL[dtype], f"residual ld {shape}")
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_vae_statistics_counting_pixels_outside_the_image_are_caught(dtype):
+    """planted: the out-of-image pixels of the partial tiles (value bias: what the epilogue holds for them) enter the sums"""
+    for shape in ((3, 9, 33, 64), (2, 17, 65, 192), (1, 5, 7, 64)):
+        n, h, w, _ = shape
+        k = V.gn_case(shape, dtype)
+        stored = V.gn_ref(shape, dtype).to(dtype)
+        want = R.stat_sums_ref(stored, n)
+        extra = -(-h // 8) * 8 * -(-w // 32) * 32 - h * w
+        b = k.bias.double()
+        planted = want + extra * torch.stack([b, b * b], -1)[None]
+        with pytest.raises(AssertionError):
+            torch.testing.assert_close(planted, want, **V.STAT_TOL)
+        leaked = want.roll(1, 0) if n > 1 else None       # records of image i under image i + 1
+        if leaked is not None:
+            with pytest.raises(AssertionError):
+                torch.testing.assert_close(leaked, want, **V.STAT_TOL)
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_vae_up2x_planted_bugs_are_caught(dtype):
+    """py / px swapped (phases 1 and 2 exchanged); the even rows' tap sums on the odd rows; image i's border reading image i - 1"""
+    for shape in V.UP_SHAPES:
+        k, want = V.up_case(shape, dtype), V.up_ref(shape, dtype)
+        nout = shape[4]
+        emul = R.up2x_ref(k.x.float(), k.w4.float(), k.bias.float()).float().reshape(-1, nout).to(dtype)     # fp32 operands; see the note below
+        _inside(emul, want, dtype, R.CONV_TOL[dtype], "conv3x3_up2x", shape)
+        bites(R.up2x_ref(k.x, k.w4[[0, 2, 1, 3]], k.bias).reshape(-1, nout), want, dtype, R.CONV_TOL[dtype], f"up2x py/px swapped {shape}")
+        bites(R.up2x_ref(k.x, k.w4[[0, 1, 0, 1]], k.bias).reshape(-1, nout), want, dtype, R.CONV_TOL[dtype], f"up2x even weights on odd rows {shape}")
+    shape = (3, 8, 32, 128, 136)
+    k, want = V.up_case(shape, dtype), V.up_ref(shape, dtype)
+    n, h, w, c, nout = shape
+    tall = R.up2x_ref(k.x.reshape(1, n * h, w, c), k.w4, k.bias).reshape(-1, nout)      # the batch as ONE tall image: borders see the neighbours
+    bites(tall, want, dtype, R.CONV_TOL[dtype], "up2x cross-image border")
+
+
+def _fp32_sum_emul(k, dtype):
+    """the phase convolutions with fp32 accumulation (torch conv2d in fp32), rounded once"""
+    n, h, w, c, nout = k.shape
+    xin = k.x.float().permute(0, 3, 1, 2)
+    out = torch.zeros(n, nout, 2 * h, 2 * w)
+    for ph in range(4):
+        py, px = ph >> 1, ph & 1
+        out[:, :, py::2, px::2] = F.conv2d(F.pad(xin, (1 - px, px, 1 - py, py)), k.w4[ph].float().view(nout, 2, 2, c).permute(0, 3, 1, 2), k.bias.float())
+    return out.permute(0, 2, 3, 1).reshape(-1, nout).to(dtype)
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_vae_up2x_fp32_emulation_meets_the_tolerance(dtype):
+    for shape in V.UP_SHAPES:
+        _inside(_fp32_sum_emul(V.up_case(shape, dtype), dtype), V.up_ref(shape, dtype), dtype, R.CONV_TOL[dtype], "conv3x3_up2x", shape)
+
+
+def _attn_operands(a, dtype):
+    """q, and k / v as the qk-halves layout holds them: rows >= nk of the image's key half are 7.0, V^T pad columns -5"""
+    rows = max(a.nq, a.nk, -(-a.nk // 32) * 32)
+    k = torch.full((a.b, rows, V.C512), 7.0, dtype=dtype)
+    v = torch.full((a.b, rows, V.C512), -5.0, dtype=dtype)
+    k[:, :a.nk], v[:, :a.nk] = a.k, a.v
+    return a.q, k, v
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_vae_attention512_emulation_meets_the_tolerance_on_every_case(dtype):
+    cases = [(b, nq, nk, None) for b, nq, nk in V.ATTN_SHAPES] + [(2, 96, nk, s) for s, nk in V.ATTN_STRUCTURES.items()]
+    for b, nq, nk, s in cases:
+        a = V.attn_case(b, nq, nk, dtype, s)
+        q, k, v = _attn_operands(a, dtype)
+        got = R.attn512_emul(q, k, v, nk, V.C512 ** -0.5, dtype).reshape(b * nq, V.C512)
+        _inside(got, V.attn_ref(b, nq, nk, dtype, s), dtype, R.ATTN_TOL[dtype], "attention512", (b, nq, nk, s))
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_vae_attention512_planted_bugs_are_caught(dtype):
+    """pad keys not masked (ragged last step); the accumulator not rescaled when the running maximum rises; k taken from the q half"""
+    sc = V.C512 ** -0.5
+    for b, nq, nk, s in ((2, 63, 31, None), (3, 65, 33, None), (2, 96, 150, "late_spike_ragged")):
+        a = V.attn_case(b, nq, nk, dtype, s)
+        q, k, v = _attn_operands(a, dtype)
+        bites(R.attn512_emul(q, k, v, nk, sc, dtype, plant="pad_keys_attend").reshape(b * nq, -1), V.attn_ref(b, nq, nk, dtype, s), dtype, R.ATTN_TOL[dtype], f"pad keys {nk}")
+    for s in ("staircase", "late_spike_ragged"):
+        nk = V.ATTN_STRUCTURES[s]
+        a = V.attn_case(2, 96, nk, dtype, s)
+        q, k, v = _attn_operands(a, dtype)
+        bites(R.attn512_emul(q, k, v, nk, sc, dtype, plant="no_rescale").reshape(2 * 96, -1), V.attn_ref(2, 96, nk, dtype, s), dtype, R.ATTN_TOL[dtype], f"no rescale {s}")
+    for b, nq, nk in ((2, 64, 32), (2, 200, 77)):
+        a = V.attn_case(b, nq, nk, dtype)
+        q, k, v = _attn_operands(a, dtype)
+        kq = torch.full_like(k, 30000.0)                 # the q half of the same rows: q, then the 30000 behind it
+        kq[:, :min(nq, k.shape[1])] = q[:, :k.shape[1]]
+        bites(R.attn512_emul(q, kq, v, nk, sc, dtype).reshape(b * nq, -1), V.attn_ref(b, nq, nk, dtype), dtype, R.ATTN_TOL[dtype], f"k from the q half {nk}")
+
+
+def test_zz_report_worst_emulation_excess():
+    """prints the worst unplanted-emulation excess per kernel and type gathered above (visible with -s): the figures beside kernel_refs.CONV_TOL"""
+    for (kernel, dtype), e in sorted(WORST.items(), key=str):
+        print(f"EMULATION {kernel} {dtype}: {e:.3f}")
+    assert all(e <= 1.0 for e in WORST.values())
+
+
+# ---- hipops.fold_up2x_weights (plain torch: runs here) -------------------------------------------------------------------------------------------
+def _fold_weights(dtype, c, nout, kind, seed):
+    g = B.gen(seed)
+    w = torch.randn(nout, 9 * c, generator=g) / math.sqrt(9 * c)
+    if kind == "binades":         # summands spread over ~24 binades, signs mixed: sums that cancel and sums whose small terms only break ties
+        w = w * torch.exp2(-torch.randint(0, 25, w.shape, generator=g).float())
+    elif kind == "ties":          # small integers times one ulp: many sums are exact rounding ties or one small summand away from one
+        w = torch.randint(-2047, 2048, w.shape, generator=g).float() * 2.0 ** -9 + torch.exp2(-torch.randint(10, 30, w.shape, generator=g).float())
+    return w.to(dtype)
+
+
+@pytest.mark.parametrize("dtype", DTS)
+@pytest.mark.parametrize("kind", ["plain", "binades", "ties"])
+@pytest.mark.parametrize("c,nout", [(64, 8), (128, 136), (192, 40)])
+def test_fold_up2x_weights_against_fp64_tap_sums(c, nout, kind, dtype):
+    """the tap sums of the 16-bit weights rounded ONCE: within 1 ulp of the fp64 sums everywhere, and bit-equal to their correct rounding wherever the
+    fp64 sum is not within 2^-30 (relative) of a rounding tie"""
+    from forge_amd import hipops as ops
+    wk = _fold_weights(dtype, c, nout, kind, 400 + c + nout)
+    got = ops.fold_up2x_weights(wk, c)
+    assert got.dtype == dtype and got.shape == (4, nout, 4 * c)
+    want = R.fold_up2x_ref(wk, c)
+    assert R.excess(got, want, dtype, 1.0, 0.0) <= 1.0
+    exact, tie = R.round_to(want, dtype)
+    clear = tie > 2.0 ** -30
+    assert int(clear.sum()) > 0.5 * clear.numel()       # (exact ties are common among sums of two 16-bit numbers; most sums are clear of them)
+    wrong = int((got.double()[clear] != exact[clear]).sum())
+    assert wrong == 0, f"{wrong} of {int(clear.sum())} tap sums are not the correctly rounded fp64 sum"
