@@ -197,7 +197,14 @@ int fmx_geglu_interleave_rows(const void* w_in, const void* b_in, void* w_out, v
  *   dpad in {48, 64, 80, 128, 160}: head dim padded to a multiple of 16 with ZERO columns (rows in vt);
  *   nk_pad = number of key columns present per (b,h,d) row of vt / rows of k (multiple of 64),
  *   nk = number of valid keys (<= nk_pad, keys >= nk are masked out).  nq arbitrary.
- *   All base pointers 16-byte aligned; strides % 8 == 0.
+ *   All base pointers 16-byte aligned; strides % 8 == 0, except o_rs: % 4 == 0 (rows of O that start on an 8-byte boundary are stored with
+ *   unaligned 16-byte accesses).
+ *   What the buffers may hold around the operands (tests/test_gpu_attention_fast.py, test_gpu_attention_generic.py):
+ *     k  rows [nk, nk_pad) of an image are read and masked by a select: anything, NaN and +-inf included.  Rows >= nk_pad are never read.
+ *     vt columns [nk, nk_pad) are multiplied by a probability of exactly 0: any FINITE value (a NaN or inf there reaches O).
+ *     q  rows >= nq are never used (the kernels clamp the row index or bound the read); they need not exist.
+ *     o  a launch writes exactly the elements (b, i < nq, h, d < dpad) and nothing else: o may be a column window of a wider buffer
+ *        (o_rs > heads * dpad) and images may lie further apart than nq rows (o_bs > nq * o_rs); rows [nq, o_bs / o_rs) keep their contents.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct fmx_attn_args {
   const void* q;

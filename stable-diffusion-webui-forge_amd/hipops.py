@@ -339,8 +339,10 @@ def strided_copy4(src, dst, dims, src_strides, dst_strides):
 
 
 def attention(q, k, vt, *, batch, heads, nq, nk, nk_pad, dpad, scale, q_bs, q_rs, k_bs, k_rs, vt_bs, vt_hs, vt_ds,
-              out=None, force32=False, causal=False, mask=None, mask_strides=(0, 0, 0)):
+              out=None, o_bs=None, force32=False, causal=False, mask=None, mask_strides=(0, 0, 0)):
     """q/k/vt are base tensors (views allowed: the data_ptr is the element (0,0,0,0)); strides in elements.
+    out: optional [rows, >= heads * dpad] view whose data_ptr is O's element (0,0,0,0) and whose stride(0) is the row stride; o_bs: element stride between
+    the images of O (default nq * out.stride(0): images back to back).
     mask: optional fp16 additive mask, element (b, h, i, j) at mask_strides = (batch, head, query) element strides, rows of nk_pad keys."""
     sfx, elem = _elem(q, k, vt, out)
     fn_name = "fmx_attention" + sfx
@@ -350,7 +352,7 @@ def attention(q, k, vt, *, batch, heads, nq, nk, nk_pad, dpad, scale, q_bs, q_rs
     a.q, a.k, a.vt, a.o = _p(q), _p(k), _p(vt), _p(out)
     a.q_bs, a.q_rs, a.k_bs, a.k_rs = q_bs, q_rs, k_bs, k_rs
     a.vt_bs, a.vt_hs, a.vt_ds = vt_bs, vt_hs, vt_ds
-    a.o_bs, a.o_rs = nq * out.stride(0), out.stride(0)
+    a.o_bs, a.o_rs = (nq * out.stride(0) if o_bs is None else int(o_bs)), out.stride(0)
     a.batch, a.heads, a.nq, a.nk, a.nk_pad, a.dpad = batch, heads, nq, nk, nk_pad, dpad
     a.scale = -float(scale) if force32 else float(scale)  # test hook: negative scale selects the 32-query-per-wave kernel
     a.zero_page = _p(zero_page(q.device))

@@ -691,3 +691,138 @@ def test_fold_up2x_weights_against_fp64_tap_sums(c, nout, kind, dtype):
     assert int(clear.sum()) > 0.5 * clear.numel()       # (exact ties are common among sums of two 16-bit numbers; most sums are clear of them)
     wrong = int((got.double()[clear] != exact[clear]).sum())
     assert wrong == 0, f"{wrong} of {int(clear.sum())} tap sums are not the correctly rounded fp64 sum"
+
+
+# ---- the 64-query attention kernels (tests/test_gpu_attention_fast.py) ---------------------------------------------------------------------------
+# kernel_refs.attn64_emul is the kernels' arithmetic in fp32 torch; it runs on every case of the GPU file in both types, unplanted (must stay inside
+# ATTN_TOL) and with one bug planted (must reach 4x on at least one case of the family the bug lives in).
+import test_gpu_attention_fast as A  # noqa: E402
+
+_A_CACHE = {}
+
+
+def _fast(case, dtype):
+    """-> (layout, buffers, fp64 reference on the CPU, route at 256 CUs) of a case, built once"""
+    key = (case.id, dtype)
+    if key not in _A_CACHE:
+        L, bufs = A.build(case, dtype)
+        _A_CACHE[key] = (L, bufs, A.reference(bufs, L, dev="cpu"), R.attn_route(case.b, case.h, case.nq, case.nk, case.d, 256))
+    return _A_CACHE[key]
+
+
+def _fast_emul(case, dtype, plant=None):
+    L, bufs, want, route = _fast(case, dtype)
+    q, k, v = A.gather(bufs, L)
+    step, split = R.attn_route_emul(route)
+    got = R.attn64_emul(q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3), L.nk, L.d ** -0.5, dtype, step=step, split=split, plant=plant)
+    return R.excess(got, want, dtype, *R.ATTN_TOL[dtype])
+
+
+_A_SMALL = [c for c in A.CASES if c.b * c.h * c.nq <= 60000]       # (the three large launches are covered by test_fast_attention_emulation... only)
+
+
+def test_fast_attention_cases_reach_every_route_at_256_cus():
+    """the case list hits every row of the route table, in both types (every case runs in fp16 and bf16), and is listed under the route it reaches"""
+    seen = {}
+    for c in A.CASES:
+        route = R.attn_route(c.b, c.h, c.nq, c.nk, c.d, 256)
+        assert route == c.route, f"{c.id}: reaches {route}, listed under {c.route}"
+        seen.setdefault(route, []).append(c.id)
+    for route in A.ROUTES:
+        print(f"ROUTE {route}: {len(seen.get(route, []))} cases x 2 types: {' '.join(seen.get(route, []))}")
+    assert set(seen) == set(A.ROUTES)
+    for lay, routes in (("unet_self", ("q64v3", "q64v2<64> whole", "q64v2<64> split", "q64v2<64> whole+split")), ("unet_cross", ("short2<2>", "short2<3>")),
+                        ("flux", ("ws<128>", "q64v2<128> split", "ws<128>+split tail"))):
+        assert {c.route for c in A.CASES if c.layout == lay} == set(routes)
+    for route in A.ROUTES:                                             # K pad rows NaN / +-inf on every kernel family
+        fam = route.split("<")[0] if route.startswith("short2") else route
+        assert any(c.opt.get("kpad") and c.route.startswith(fam) for c in A.CASES), route
+
+
+def test_attn_route_restates_the_dispatcher():
+    """spot values of the rule (csrc/fmx_attention.hip launch_attn_v2) at 256 and at 304 CUs"""
+    assert R.attn_route(16, 20, 1024, 1024, 64, 256) == "q64v2<64> whole"         # 1280 entries = 2.5 rounds: 256 left, more than 3/8 of the slots
+    assert R.attn_route(8, 20, 1024, 1024, 64, 256) == "q64v2<64> whole+split"    # 640 = 512 + 128
+    assert R.attn_route(16, 10, 4096, 77, 64, 256) == "short2<3>"
+    assert R.attn_route(2, 24, 4352, 4352, 128, 256) == "ws<128>+split tail"        # 816 = 3 rounds of 256 + 48
+    assert R.attn_route(1, 24, 4352, 4352, 128, 256) == "ws<128>"                  # 408 = 256 + 152: too many left to split
+    assert R.attn_route(1, 24, 1024, 1024, 128, 256) == "q64v2<128> split"
+    assert R.attn_route(2, 3, 255, 77, 64, 256) == "generic" and R.attn_route(2, 3, 300, 77, 80, 256) == "generic"
+    assert R.attn_route(2, 5, 52 * 256 - 37, 250, 64, 304) == "q64v3"              # 520 entries in one round of 608 slots, 520 > 3/8 of them: four whole tiles
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_fast_attention_emulation_meets_the_tolerance_on_every_case(dtype):
+    for c in A.CASES:
+        e = _fast_emul(c, dtype)
+        fam = "attention " + c.route
+        WORST[(fam, dtype)] = max(WORST.get((fam, dtype), 0.0), e)
+        assert e <= 1.0, f"{c.id}: the unplanted emulation is {e:.3g}x ATTN_TOL"
+        if c.b * c.h * c.nq > 60000:
+            _A_CACHE.pop((c.id, dtype), None)
+    for (fam, dt), e in sorted(WORST.items(), key=str):
+        if fam.startswith("attention ") and dt == dtype:
+            print(f"EMULATION {fam} {dtype}: {e:.3f}")
+
+
+_A_PLANTS = {  # plant -> the cases it has to show on (any one of them reaching 4x is enough)
+    "pad_keys_attend": lambda c: c.nk % 64 != 0 and c.structure is None,
+    "no_rescale": lambda c: c.structure in ("staircase", "threshold_edge", "dominant") and not c.route.startswith("short2"),
+    "never_move": lambda c: c.structure in ("dominant", "dom_upper") and not c.route.startswith("short2"),
+    "merge_unweighted": lambda c: c.structure in ("dom_lower", "dom_upper"),
+    "split_tail_unmasked": lambda c: "split" in c.route and c.nk % 64 != 0,
+}
+
+
+@pytest.mark.parametrize("dtype", DTS)
+@pytest.mark.parametrize("plant", sorted(_A_PLANTS))
+def test_fast_attention_planted_bugs_are_caught(plant, dtype):
+    """every route family the bug can live in shows it at >= 4x ATTN_TOL on at least one of its cases"""
+    cases = [c for c in _A_SMALL if _A_PLANTS[plant](c)]
+    fams = {}
+    for c in cases:
+        fams[c.route] = max(fams.get(c.route, 0.0), _fast_emul(c, dtype, plant))
+    print(f"PLANT {plant} {dtype}: " + ", ".join(f"{r} {e:.3g}" for r, e in sorted(fams.items())))
+    assert fams and all(e >= TEETH for e in fams.values()), fams
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_fast_attention_q_scaled_without_the_second_rounding_is_not_resolved(dtype):
+    """Q scaled in fp32 and NOT rounded again (one rounding site fewer than the kernels) stays inside the tolerance on every case: this file cannot tell
+    the two apart, the difference is one rounding of Q"""
+    worst = max(_fast_emul(c, dtype, "scale_after_rounding") for c in _A_SMALL)
+    print(f"PLANT scale_after_rounding {dtype}: worst {worst:.3f}")
+    assert worst <= 1.0
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_fast_attention_layout_plants_are_caught(dtype):
+    """q read from the k half of the q | k buffer; V^T rows taken B * n apart instead of m_tok"""
+    for c in (c for c in _A_SMALL if c.layout == "unet_self"):
+        L, bufs, want, _ = _fast(c, dtype)
+        bites(A.reference(bufs, L, dev="cpu", q_from_k=True), want, dtype, R.ATTN_TOL[dtype], f"{c.id}: q from the k half")
+        bites(A.reference(bufs, L, dev="cpu", vt_ds=L.vt_ds_wrong), want, dtype, R.ATTN_TOL[dtype], f"{c.id}: vt_ds = B * n")
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_fast_attention_stores_outside_the_window_trip_the_sentinel_rule(dtype):
+    """a correct scatter leaves the surroundings alone; rows [nq, l_pad) written (O addressed as if every image had l_pad queries) and one 16-byte
+    store past the column window each change sentinel elements"""
+    for c in (c for c in _A_SMALL if c.layout != "dense"):
+        L, bufs, want, _ = _fast(c, dtype)
+        after = bufs["o"].clone()
+        A._view(after, L, "o", L.nq)[:] = want.permute(0, 2, 1, 3).to(dtype)
+        assert A.window_violations(bufs["o"], after, L) == 0
+        if c.layout == "flux":
+            spill = after.clone()
+            A._view(spill, L, "o", L.nk_pad)[:, L.nq:] = 0.5
+            assert A.window_violations(bufs["o"], spill, L) == (L.nk_pad - L.nq) * L.b * L.h * L.d
+        else:
+            spill = after.clone()
+            at = L.o_off + (L.nq - 1) * L.o_rs + L.h * L.d           # the 8 elements behind the last window column of image 0's last row
+            spill[at:at + min(8, L.o_rs - L.h * L.d)] = 0.5
+            assert A.window_violations(bufs["o"], spill, L) == min(8, L.o_rs - L.h * L.d)
+            if L.o_rs - L.h * L.d < 8:                                 # the rest of a 16-byte store lands in the next row's window: values must catch it
+                spill[at:at + 8] = 0.5
+                got = A._view(spill, L, "o", L.nq).permute(0, 2, 1, 3)
+                assert R.excess(got, want, dtype, *R.ATTN_TOL[dtype]) >= TEETH
