@@ -42,6 +42,9 @@
  *                          T2I-Adapter Downsample + ReLU backend/nn/cnets/t2i_adapter.py:42-62,76-101 ; CLIP quick-GELU / GELU
  *   fmx_embed_tokens       CLIP token + position embedding (transformers CLIPTextEmbeddings, called from backend/nn/clip.py)
  *   fmx_vae_sample_posterior  DiagonalGaussianDistribution.sample + process_in backend/nn/vae.py:16-29,312-313
+ *   fmx_conv3x3_c64_f16 / fmx_taesd_pack_latent / fmx_latent_rgb
+ *                          the TAESD decoder modules/sd_vae_taesd.py:16-44 (live previews modules/sd_samplers_common.py:36-93,123-128 and the "TAESD"
+ *                          decode method) ; cheap_approximation modules/sd_vae_approx.py:73-74
  *   fmx_*_bf16             the bfloat16 build of the Flux path's kernels (last section)
  *   fmx_gguf_dequant_*     GGUF checkpoints: backend/utils.py:27-31 (load_torch_file), backend/operations_gguf.py (dequantize_tensor,
  *                          quants_mapping), backend/loader.py:181-211 (replace_state_dict), packages_3rdparty/gguf/quants.py (dequantize_blocks)
@@ -437,6 +440,23 @@ int fmx_conv3x3_up2x_f16(const void* x, int32_t n, int32_t h, int32_t w, int32_t
 int fmx_conv3x3_narrow_gn_silu_f16(const void* x, int32_t n, int32_t h, int32_t w, int32_t c, const float* x_partial, int32_t x_nchunks, int32_t groups, float eps,
                                    const void* gamma, const void* beta, float* scale_shift, const void* wgt, const void* bias, int32_t nout, void* out,
                                    int32_t ld_out, void* stream);
+/* 3x3 convolution (stride 1, zero padding 1), 64 -> 64 channels, with the epilogues of the TAESD decoder (modules/sd_vae_taesd.py:16-44: conv + ReLU, the Block's
+ * `fuse(conv(x) + skip(x))`, `nn.Upsample(scale_factor=2)` + conv).  New symbols, the ABI number does not move.
+ *   out[m][o] = act(bias[o] + residual[m][o] + sum_{ky,kx,c} wgt[o][ky][kx][c] * xin[pixel(m) + (ky-1, kx-1)][c])      (xin zero outside the oh x ow image)
+ * x 16-bit NHWC [n][h][w][64] dense; wgt [64][ky][kx][64] (the GEMM entry's layout); bias [64] or null; residual [n*oh*ow][ld_res] or null; relu 0 / 1: act =
+ * ReLU, applied AFTER the residual add; up2x 0: (oh, ow) = (h, w) and xin = x; up2x 1: (oh, ow) = (2h, 2w) and xin[Y][X] = x[Y >> 1][X >> 1], the nearest
+ * upsample in front of the convolution, staged from the half-resolution source with the layer's own weights (no tap-sum fold, no extra rounding site);
+ * out [n*oh*ow][ld_out].  fp32 accumulation, one rounding.  cin and cout must both be 64 (FMX_E_BADARG otherwise, before any launch); x and wgt 16-byte
+ * aligned; out / residual / bias 8-byte aligned, ld_out and ld_res multiples of 4.  A direct kernel: one persistent workgroup per CU keeps all nine taps
+ * of the weight in LDS and walks 8 x 32-pixel output tiles, whose input patches are staged once each (double-buffered) instead of gathered nine times. */
+int fmx_conv3x3_c64_f16(const void* x, int32_t n, int32_t h, int32_t w, int32_t cin, const void* wgt, const void* bias, int32_t cout, const void* residual,
+                        int64_t ld_res, int32_t relu, int32_t up2x, void* out, int64_t ld_out, void* stream);
+/* TAESD input (modules/sd_vae_taesd.py:20-23 Clamp behind modules/sd_samplers_common.py:60 `sample.to(devices.dtype)`): latent fp32 NCHW [b][c][h][w], c <= 64
+ * -> tanh(round16(z) / 3) * 3 (fp32 arithmetic, one rounding) as fp16 NHWC [b*h*w][64], channels >= c zeros */
+int fmx_taesd_pack_latent(const float* z, int32_t b, int32_t c, int32_t h, int32_t w, void* out, void* stream);
+/* sd_vae_approx.cheap_approximation (modules/sd_vae_approx.py:73-74): out[b][r][p] = sum_l z[b][l][p] * factors[l][r], fp32 NCHW in ([b][l][npix]) and out
+ * ([b][3][npix]); factors: HOST array [l][3], l <= 64 (passed to the kernel by value: no copy, nothing to keep alive) */
+int fmx_latent_rgb(const float* z, const float* factors /* host */, int32_t b, int32_t l, int64_t npix, float* out, void* stream);
 /* VAE output: y fp16 NHWC [b*h*w][ld] (first c channels) -> clamp((y+1)/2, 0, 1) fp32 NHWC [b][h][w][c] */
 int fmx_vae_unpack_image(const void* y, int32_t ld, int64_t npix, int32_t c, float* out, void* stream);
 
@@ -503,6 +523,9 @@ int fmx_conv3x3_narrow_gn_silu_bf16(const void* x, int32_t n, int32_t h, int32_t
 int fmx_conv3x3_up2x_bf16(const void* x, int32_t n, int32_t h, int32_t w, int32_t c, const void* wgt4, const void* bias, int32_t nout, void* out,
                           float* stats, int32_t stats_cap, int32_t* stats_nchunks, const void* zero_page, void* stream);
 int fmx_conv3x3_gn_silu_bf16(const fmx_conv_gn_args* args /* host */, int32_t* stats_nchunks /* host, may be null */, void* stream);
+int fmx_conv3x3_c64_bf16(const void* x, int32_t n, int32_t h, int32_t w, int32_t cin, const void* wgt, const void* bias, int32_t cout, const void* residual,
+                         int64_t ld_res, int32_t relu, int32_t up2x, void* out, int64_t ld_out, void* stream);
+int fmx_taesd_pack_latent_bf16(const float* z, int32_t b, int32_t c, int32_t h, int32_t w, void* out, void* stream);
 int fmx_vae_sample_posterior_bf16(const void* moments, int32_t ld, const float* noise, int32_t b, int32_t lc, int64_t npix, float scale,
                                   float shift, float* out, void* stream);
 

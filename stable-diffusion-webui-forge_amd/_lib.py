@@ -132,6 +132,9 @@ SIGNATURES = {
     "fmx_conv3x3_narrow_gn_silu_f16": [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp],
     "fmx_conv3x3_up2x_f16": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, C.POINTER(C.c_int32), _vp, _vp],
     "fmx_conv3x3_gn_silu_f16": [C.POINTER(ConvGnArgs), C.POINTER(C.c_int32), _vp],
+    "fmx_conv3x3_c64_f16": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _vp, _i64, _vp],
+    "fmx_taesd_pack_latent": [_vp, _i32, _i32, _i32, _i32, _vp, _vp],
+    "fmx_latent_rgb": [_vp, C.POINTER(C.c_float), _i32, _i32, _i64, _vp, _vp],
     "fmx_blend_masked": [_vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "fmx_count_nonfinite_f16": [_vp, _i64, _vp, _vp],
     "fmx_vae_sample_posterior": [_vp, _i32, _vp, _i32, _i32, _i64, _f32, _f32, _vp, _vp],
@@ -157,6 +160,9 @@ for _n in ("fmx_gemm_conv_stats", "fmx_groupnorm_stats", "fmx_groupnorm_apply", 
     SIGNATURES[_n + "_bf16"] = SIGNATURES[_n + "_f16"]
 for _n in ("fmx_vae_pack_latent", "fmx_vae_unpack_image", "fmx_vae_sample_posterior"):
     SIGNATURES[_n + "_bf16"] = SIGNATURES[_n]
+# the TAESD decoder (new symbols, the ABI number does not move)
+SIGNATURES["fmx_conv3x3_c64_bf16"] = SIGNATURES["fmx_conv3x3_c64_f16"]
+SIGNATURES["fmx_taesd_pack_latent_bf16"] = SIGNATURES["fmx_taesd_pack_latent"]
 # GGUF block dequantisation at load time (qtype, blocks, out, n_elements, stream): new symbols, the ABI number does not move
 for _n in ("fmx_gguf_dequant_f16", "fmx_gguf_dequant_bf16"):
     SIGNATURES[_n] = [_i32, _vp, _vp, _i64, _vp]

@@ -22,6 +22,8 @@
 #define fmx_conv3x3_gn_silu_f16 fmx_conv3x3_gn_silu_bf16
 #define fmx_conv3x3_up2x_f16 fmx_conv3x3_up2x_bf16
 #define fmx_conv3x3_narrow_gn_silu_f16 fmx_conv3x3_narrow_gn_silu_bf16
+// the TAESD decoder's 64 -> 64 convolution (fmx_conv_c64.hip)
+#define fmx_conv3x3_c64_f16 fmx_conv3x3_c64_bf16
 // host-side C++ symbols shared between the GEMM files
 #define fmx_launch_gemm256p fmx_launch_gemm256p_bf16
 #define fmx_launch_gemm4w fmx_launch_gemm4w_bf16

@@ -358,6 +358,47 @@ __global__ void vae_unpack_image_kernel(const T* __restrict__ y, int ld, long np
   }
 }
 
+// TAESD's input half (modules/sd_vae_taesd.py:20-23 Clamp, behind `sample.to(devices.dtype)` of modules/sd_samplers_common.py:60): the
+// latent rounded to the element type, tanh(x / 3) * 3 of that in fp32, rounded once; NHWC with 64 channels, those >= c as zeros
+template <typename T>
+__global__ void taesd_pack_latent_kernel(const float* __restrict__ z, int b, int c, int h, int w, T* __restrict__ out) {
+  const long total = (long)b * h * w * 64;
+  const long hw = (long)h * w;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int ch = (int)(i & 63);
+    const long pix = i >> 6;
+    const long bi = pix / hw, p = pix - bi * hw;
+    T o = (T)0.f;
+    if (ch < c) {
+      const float xr = (float)(T)z[(bi * c + ch) * hw + p];
+      o = (T)(tanhf(xr / 3.0f) * 3.0f);
+    }
+    out[i] = o;
+  }
+}
+
+// sd_vae_approx.cheap_approximation (modules/sd_vae_approx.py:73-74): einsum("...lxy,lr -> ...rxy") with an [L][3] table, fp32
+struct LatentRgbFactors {
+  float f[64][3];
+};
+__global__ void latent_rgb_kernel(const float* __restrict__ z, const LatentRgbFactors fac, int b, int l, long npix, float* __restrict__ out) {
+  const long total = (long)b * npix;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long bi = i / npix, p = i - bi * npix;
+    float r0 = 0.f, r1 = 0.f, r2 = 0.f;
+    for (int k = 0; k < l; ++k) {
+      const float v = z[(bi * l + k) * npix + p];
+      r0 = fmaf(v, fac.f[k][0], r0);
+      r1 = fmaf(v, fac.f[k][1], r1);
+      r2 = fmaf(v, fac.f[k][2], r2);
+    }
+    float* o = out + bi * 3 * npix + p;
+    o[0] = r0;
+    o[npix] = r1;
+    o[2 * npix] = r2;
+  }
+}
+
 __global__ void blend_masked_kernel(const float* a, const float* am, const float* b, const float* bm, float* out, long n) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) out[i] = a[i] * am[i] + b[i] * bm[i];
 }
@@ -669,6 +710,31 @@ extern "C" int fmx_vae_unpack_image(const void* y, int32_t ld, int64_t npix, int
 }
 extern "C" int fmx_vae_unpack_image_bf16(const void* y, int32_t ld, int64_t npix, int32_t c, float* out, void* stream) {
   return vae_unpack_image_impl<__bf16>(y, ld, npix, c, out, stream);
+}
+
+template <typename T>
+static int taesd_pack_latent_impl(const float* z, int32_t b, int32_t c, int32_t h, int32_t w, void* out, void* stream) {
+  FMX_REQUIRE(z && out && b > 0 && c > 0 && c <= 64 && h > 0 && w > 0, "taesd_pack_latent: bad args (1..64 latent channels)");
+  const long total = (long)b * h * w * 64;
+  hipLaunchKernelGGL(taesd_pack_latent_kernel<T>, dim3(grid_for(total)), dim3(TPB), 0, (hipStream_t)stream, z, b, c, h, w, (T*)out);
+  FMX_LAUNCH_CHECK("fmx_taesd_pack_latent");
+  return FMX_OK;
+}
+extern "C" int fmx_taesd_pack_latent(const float* z, int32_t b, int32_t c, int32_t h, int32_t w, void* out, void* stream) {
+  return taesd_pack_latent_impl<f16>(z, b, c, h, w, out, stream);
+}
+extern "C" int fmx_taesd_pack_latent_bf16(const float* z, int32_t b, int32_t c, int32_t h, int32_t w, void* out, void* stream) {
+  return taesd_pack_latent_impl<__bf16>(z, b, c, h, w, out, stream);
+}
+
+extern "C" int fmx_latent_rgb(const float* z, const float* factors, int32_t b, int32_t l, int64_t npix, float* out, void* stream) {
+  FMX_REQUIRE(z && factors && out && b > 0 && l > 0 && l <= 64 && npix > 0, "latent_rgb: bad args (1..64 latent channels)");
+  LatentRgbFactors fac;
+  for (int k = 0; k < 64; ++k)
+    for (int r = 0; r < 3; ++r) fac.f[k][r] = k < l ? factors[k * 3 + r] : 0.f;
+  hipLaunchKernelGGL(latent_rgb_kernel, dim3(grid_for((long)b * npix)), dim3(TPB), 0, (hipStream_t)stream, z, fac, b, l, (long)npix, out);
+  FMX_LAUNCH_CHECK("fmx_latent_rgb");
+  return FMX_OK;
 }
 
 extern "C" int fmx_count_nonfinite_f16(const void* x, int64_t n, int32_t* count, void* stream) {

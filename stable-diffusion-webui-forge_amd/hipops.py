@@ -814,6 +814,59 @@ def conv3x3_narrow(x, wgt, bias, nout, out=None, ld_out=4):
     return out
 
 
+def conv3x3_c64(x, wgt, bias=None, *, residual=None, relu=False, up2x=False, out=None):
+    """3x3 convolution 64 -> 64 channels (stride 1, padding 1), direct kernel (fmx_conv3x3_c64): x NHWC [n, h, w, 64], wgt [64, 9 * 64] in the GEMM's
+    tap-major layout -> act(bias + residual + conv) as [n * oh * ow, ld_out]; relu after the residual add; up2x: the convolution runs on the x2 nearest
+    upsample of x ((oh, ow) = (2h, 2w)), staged from x itself.  residual / out may be row-strided 2-D windows of wider buffers (stride(0) % 4 == 0)."""
+    sfx, elem = _elem(x, wgt, bias, residual, out)
+    n, h, w, c = x.shape
+    if not x.is_contiguous():
+        raise ValueError("conv3x3_c64: x must be dense NHWC")
+    m = n * (h << int(up2x)) * (w << int(up2x))
+    if out is None:
+        out = empty((m, 64), elem, x.device)
+    for t in (out, residual):
+        if t is not None and (t.dim() != 2 or t.shape[0] != m or t.shape[1] < 64 or t.stride(1) != 1):
+            raise ValueError("conv3x3_c64: out / residual must be [n * oh * ow, >= 64] with unit column stride")
+    name = "fmx_conv3x3_c64" + sfx
+
+    def run():
+        _lib.check(getattr(_lib.lib(), name)(_p(x), n, h, w, c, _p(wgt), _p(bias), wgt.shape[0], _p(residual), residual.stride(0) if residual is not None else 0,
+                                             int(bool(relu)), int(bool(up2x)), _p(out), out.stride(0), stream_ptr()), name)
+    if _profiler is not None:   # one read of the input (a quarter of it with up2x) and of the residual, one write of the output
+        _profiler.launch("conv3x3_c64", 2.0 * m * 9 * 64 * 64, run, tag=f"N={n} H={h} W={w} up2x={int(up2x)} relu={int(relu)} res={int(residual is not None)}",
+                         nbytes=2.0 * 64 * (n * h * w + m * (2 if residual is not None else 1)))
+    else:
+        run()
+    return out
+
+
+def taesd_pack_latent(z, out=None, dtype=torch.float16):
+    """fp32 NCHW latent [b, L, h, w] (L <= 64) -> tanh(round(z) / 3) * 3 as NHWC [b, h, w, 64] of `dtype`, channels >= L zero (fmx_taesd_pack_latent)"""
+    if z.dtype != torch.float32 or not z.is_cuda or not z.is_contiguous():
+        raise TypeError("taesd_pack_latent expects a contiguous fp32 device tensor")
+    b, c, h, w = z.shape
+    if out is None:
+        out = empty((b, h, w, 64), dtype, z.device)
+    name = "fmx_taesd_pack_latent" + _vae_sfx(out.dtype)
+    _lib.check(getattr(_lib.lib(), name)(_p(z), b, c, h, w, _p(out), stream_ptr()), name)
+    return out
+
+
+def latent_rgb(z, factors, out=None):
+    """einsum("blxy,lr -> brxy") of an fp32 NCHW latent with a host [L][3] table (list / tensor), fp32 (fmx_latent_rgb)"""
+    if z.dtype != torch.float32 or not z.is_cuda or not z.is_contiguous():
+        raise TypeError("latent_rgb expects a contiguous fp32 device tensor")
+    b, l, h, w = z.shape
+    flat = [float(v) for row in (factors.tolist() if hasattr(factors, "tolist") else factors) for v in row]
+    if len(flat) != l * 3:
+        raise ValueError(f"latent_rgb: the factor table must be [{l}][3], got {len(flat)} values")
+    if out is None:
+        out = torch.empty((b, 3, h, w), dtype=torch.float32, device=z.device)
+    _lib.check(_lib.lib().fmx_latent_rgb(_p(z), (C.c_float * len(flat))(*flat), b, l, h * w, _p(out), stream_ptr()), "fmx_latent_rgb")
+    return out
+
+
 # A/B knob: FMX_UP2X=0 keeps the Upsample convolutions on the implicit GEMM with nearest-upsample-on-load (9 taps per output pixel, round 4's path)
 _UP2X = _lib.knob("FMX_UP2X", "1") != "0"
 

@@ -25,7 +25,10 @@ class Processed:
 
 
 def decode_first_stage(model, x):
-    return model.decode_first_stage(x)
+    """processing.py:620-625 -> sd_samplers_common.decode_first_stage: opts.sd_vae_decode_method picks the decoder of final images (hires passes
+    included); "Full" (the default) is model.decode_first_stage(x)"""
+    from . import sd_samplers_common
+    return sd_samplers_common.decode_first_stage(model, x)
 
 
 def decode_latent_batch(model, batch, target_device=None, check_for_nans=False):

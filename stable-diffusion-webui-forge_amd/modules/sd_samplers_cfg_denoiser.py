@@ -77,7 +77,9 @@ class CFGDenoiser:
         if self.mask is not None:
             denoised = ops.blend_masked(denoised, self._nmask32(x), self.init_latent, self._mask32(x))  # :204-213
         self.sampler.last_latent = denoised
-        state.current_latent = denoised
+        # :216 store_latent: current_latent, and -- live previews on and the step due -- the preview of sample 0, here and now: on this stream, outside
+        # any captured graph (the UNet's graph has been replayed; `denoised` may be overwritten by the next replay).  Previews off: no launch, no sync
+        sd_samplers_common.store_latent(denoised)
         self.step += 1
         if self.classic_ddim_eps_estimation:
             return ops.lincomb([x, denoised], [1.0 / sig0, -1.0 / sig0])  # :224-226 eps = (x - denoised) / sigma

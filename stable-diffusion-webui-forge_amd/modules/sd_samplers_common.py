@@ -1,8 +1,10 @@
 """Mirror of modules/sd_samplers_common.py for the path: `SamplerData` (:13-31), `InterruptedException` (:186),
-`TorchHijack` (:214-235), `Sampler` base (:238-364: callback_state, launch_sampling, initialize)."""
+`TorchHijack` (:214-235), `Sampler` base (:238-364: callback_state, launch_sampling, initialize), and the latent -> picture helpers behind
+live previews and the VAE decode method (:36-93, :123-128)."""
 import inspect
 from collections import namedtuple
 
+import numpy as np
 import torch
 
 from . import shared
@@ -33,9 +35,74 @@ def setup_img2img_steps(p, steps=None):
     return steps, t_enc
 
 
+approximation_indexes = {"Full": 0, "Approx NN": 1, "Approx cheap": 2, "TAESD": 3}   # sd_samplers_common.py:36
+
+
+def samples_to_images_tensor(sample, approximation=None, model=None):
+    """sd_samplers_common.py:39-67: latents [B, L, h, w] -> RGB image tensors [B, 3, H, W] in about [-1, 1].  approximation None: the live-preview
+    method (opts.show_progress_type; "Full" there means "Approx NN").  "Approx NN" (sd_vae_approx.VAEApprox) is not built and falls back to the
+    cheap approximation, as the reference does when `sd_vae_approx.model()` returns None; `live_preview_fast_interrupt` is not mirrored."""
+    from . import sd_vae_approx, sd_vae_taesd
+    if approximation is None:
+        approximation = approximation_indexes.get(shared.opts.show_progress_type, 0)
+        if approximation == 0:
+            approximation = 1
+    if approximation in (1, 2):
+        return sd_vae_approx.cheap_approximation(sample)
+    if approximation == 3:
+        # TAESD takes the RAW latent (no process_out) and returns about [0, 1] (:56-61)
+        return sd_vae_taesd.decoder_model().decode(sample) * 2 - 1
+    if model is None:
+        model = shared.sd_model
+    return model.decode_first_stage(sample)
+
+
+def single_sample_to_image(sample, approximation=None):
+    """sd_samplers_common.py:70-80: one latent [L, h, w] -> PIL.Image"""
+    from PIL import Image
+    x_sample = samples_to_images_tensor(sample.unsqueeze(0), approximation)[0] * 0.5 + 0.5
+    x_sample = x_sample.float().cpu()
+    x_sample.clamp_(0.0, 1.0)
+    x_sample.mul_(255.)
+    x_sample.round_()
+    x_sample = x_sample.to(torch.uint8)
+    x_sample = np.moveaxis(x_sample.numpy(), 0, 2)
+    return Image.fromarray(x_sample)
+
+
+def decode_first_stage(model, x):
+    """sd_samplers_common.py:83-85: the decode of final images by opts.sd_vae_decode_method"""
+    approx_index = approximation_indexes.get(shared.opts.sd_vae_decode_method, 0)
+    return samples_to_images_tensor(x, approx_index, model)
+
+
+def sample_to_image(samples, index=0, approximation=None):
+    return single_sample_to_image(samples[index], approximation)      # :88-89
+
+
+def preview_due():
+    """the period rule of store_latent (:126): previews on, a positive period, and the sampling step a multiple of it.  Reads three attributes: with
+    previews off nothing is launched and nothing synchronises"""
+    opts = shared.opts
+    return bool(opts.live_previews_enable) and opts.show_progress_every_n_steps > 0 and shared.state.sampling_step % opts.show_progress_every_n_steps == 0
+
+
+def store_latent(decoded):
+    """sd_samplers_common.py:123-128.  The preview is made right here, on the caller's stream and outside any captured graph: `decoded` may live in a
+    graph's memory pool that the next replay overwrites."""
+    shared.state.current_latent = decoded
+    if preview_due():
+        if not shared.parallel_processing_allowed:
+            shared.state.assign_current_image(sample_to_image(decoded))
+
+
 def images_tensor_to_samples(image, approximation=None, model=None):
-    """sd_samplers_common.py:96-120 ("Full" VAE encode only): image [B,3,H,W] in [0, 1] -> latent, one image at a time as the
-    reference does (each draws its own posterior noise from the CPU default generator, nn/vae.py:28)."""
+    """sd_samplers_common.py:96-120 ("Full" VAE encode only; the TAESD encoder is not built): image [B,3,H,W] in [0, 1] -> latent, one image at a
+    time as the reference does (each draws its own posterior noise from the CPU default generator, nn/vae.py:28)."""
+    if approximation is None:
+        approximation = approximation_indexes.get(getattr(shared.opts, "sd_vae_encode_method", "Full"), 0)
+    if approximation == 3:
+        raise NotImplementedError('sd_vae_encode_method = "TAESD": the TAESD encoder (modules/sd_vae_taesd.py:47-54, :134-158) is not built; use "Full"')
     model = model if model is not None else shared.sd_model
     image = image.to(model.device, dtype=torch.float32) * 2 - 1
     if len(image) > 1:

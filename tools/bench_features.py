@@ -4,6 +4,8 @@ per-block hooks (eager path), AND-composed prompts, hires-fix second pass.  Not 
 §8f rows hold up at the BASELINE shape -- arena sizing, 32-bit offsets, graph capture with other batch sizes -- and what they cost.
 
     python tools/bench_features.py [--steps 6] [--only samplers,controlnet,hooks,and,hires]
+    python tools/bench_features.py --only taesd      the TAESD decode of batch x (res/8)^2 SDXL-shaped latents (synthetic weights, fp16) next to the Full
+                                                     VAE decode of the same latents in the same process: median of 5 after warm-up, events around the calls
 """
 import argparse
 import json
@@ -25,6 +27,39 @@ from forge_amd.backend.nn.layout import controlnet_param_shapes, unet_param_shap
 from forge_amd.modules import processing, prompt_parser as pp, shared  # noqa: E402
 
 
+def taesd_leg(batch, width, height, dev):
+    from forge_amd.backend.nn.layout import vae_decoder_param_shapes
+    from forge_amd.backend.nn.taesd import TAESDDecoder, expected_keys
+    from forge_amd.backend.nn.vae import IntegratedAutoencoderKL
+    g = torch.Generator("cpu").manual_seed(5)
+    sd = {}
+    for k in expected_keys():     # He-scaled: the depth keeps its scale in fp16
+        shape = (64,) if k.endswith("bias") else (3 if k.startswith("19.") else 64, 4 if k == "1.weight" else 64, 3, 3)
+        sd[k] = torch.randn(shape, generator=g) * (0.1 if k.endswith("bias") else (2.0 / (shape[1] * 9)) ** 0.5)
+    tae = TAESDDecoder(sd, device=dev, dtype=torch.float16)
+    vcfg = synth.SDXL_VAE_CONFIG
+    vae = IntegratedAutoencoderKL(vcfg, synth.synth_state_dict_device(vae_decoder_param_shapes(vcfg), 1, dev), device=dev)
+    z = torch.randn(batch, 4, height // 8, width // 8, generator=g).to(dev)
+
+    def timed(fn):
+        for _ in range(2):
+            out = fn()
+        ms = []
+        for _ in range(5):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            out = fn()
+            b.record()
+            torch.cuda.synchronize()
+            ms.append(a.elapsed_time(b))
+        return sorted(ms)[2], out
+    t_ms, img = timed(lambda: tae.decode(z))
+    f_ms, full = timed(lambda: vae.decode(vae.process_out(z)))
+    print(json.dumps({"case": "TAESD decode vs Full VAE decode", "latent": list(z.shape), "dtype": "f16", "taesd_ms": round(t_ms, 3), "full_ms": round(f_ms, 3),
+                      "full_over_taesd": round(f_ms / t_ms, 2), "finite": bool(torch.isfinite(img).all() and torch.isfinite(full).all()),
+                      "taesd_out": list(img.shape)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=6)
@@ -36,6 +71,10 @@ def main():
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     width, height = a.width or a.res, a.height or a.res
+    if "taesd" in a.only.split(","):
+        taesd_leg(a.batch, width, height, dev)
+        if a.only == "taesd":
+            return
     cfg = synth.SDXL_UNET_CONFIG
     eng = build_engine(cfg, synth.synth_state_dict_device(unet_param_shapes(cfg), 0, dev), None, None, device=dev)
     b = a.batch
