@@ -58,7 +58,7 @@
 extern "C" {
 #endif
 
-#define FMX_ABI_VERSION 11
+#define FMX_ABI_VERSION 12
 
 #define FMX_OK 0
 #define FMX_E_BADARG 10001   /* shape / alignment / null-pointer contract violated */
@@ -233,6 +233,12 @@ typedef struct fmx_attn_args {
 } fmx_attn_args;
 
 int fmx_attention_f16(const fmx_attn_args* args /* host */, void* stream);
+
+/* Which kernel(s) fmx_attention_f16 / _bf16 would launch for `args` on a device of `cus` compute units, with no development knob set (ABI 12).
+ * Host only: validates like fmx_attention_f16, launches nothing, touches no device.  Writes one of "generic" (the 32-query kernel: every masked,
+ * causal or scale < 0 call, d_head 48 / 80 / 160, fewer than 256 queries, K / V^T / Q spans that do not fit 32-bit byte offsets), "short2<NB>",
+ * "q64v3", "q64v2<D> whole", "q64v2<D> split", "q64v2<D> whole+split", "ws<128>" or "ws<128>+split tail" (two launches) into buf[cap]. */
+int fmx_attention_route(const fmx_attn_args* args /* host */, int32_t cus, char* buf, int32_t cap);
 
 /* Fused attention of ONE head of width 512 (the VAE mid-block attention: backend/nn/vae.py:118-137 -> attention.py:412-422), N up to 16 384
  * tokens, without materialising the scores: O = softmax(Q K^T * scale) V, the head dimension split across the waves of a workgroup.

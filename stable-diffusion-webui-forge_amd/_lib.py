@@ -98,6 +98,7 @@ SIGNATURES = {
     "fmx_layernorm_rowstats_finalize": [_vp, _i32, _i64, _i32, _f32, _vp, _vp],
     "fmx_geglu_interleave_rows": [_vp, _vp, _vp, _vp, _i32, _i32, _vp],
     "fmx_attention_f16": [C.POINTER(AttnArgs), _vp],
+    "fmx_attention_route": [C.POINTER(AttnArgs), _i32, C.c_char_p, _i32],
     "fmx_softmax_rows_f16": [_vp, _i64, _i32, _i64, _vp],
     "fmx_attention_single_head512_f16": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _vp],
     "fmx_groupnorm_stats_f16": [_vp, _i32, _i64, _i32, _i32, _vp, _i32, _vp],
@@ -246,7 +247,7 @@ def lib():
             handle.fmx_build_info.restype = C.c_char_p
         except AttributeError as e:
             raise FmxError(f"symbol fmx_build_info missing from {LIB_PATH}") from e
-        if handle.fmx_abi_version() != 11:
+        if handle.fmx_abi_version() != 12:
             raise FmxError("libfmx ABI version mismatch")
         _lib = handle
     return _lib

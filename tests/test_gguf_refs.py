@@ -115,4 +115,4 @@ def test_entry_point_contract(lib, fn):
     assert f(8, p, p, 0, None) == 10001 and f(8, p, p, -32, None) == 10001
     assert f(8, C.c_void_p(FAKE + 1), p, 32, None) == 10001 and "2-byte" in err()
     assert f(8, p, C.c_void_p(FAKE + 2), 32, None) == 10001 and "16-byte" in err()
-    assert lib.fmx_abi_version() == 11
+    assert lib.fmx_abi_version() == 12

@@ -1,12 +1,14 @@
 """GPU (MI355X) parity of the 64-query attention kernels behind fmx_attention_f16 / _bf16 (csrc/fmx_attention.hip): every unmasked, non-causal call at
 d_head 64 / 128 with >= 256 queries -- attn_short2_kernel<1..4> (d 64, <= 128 keys), attn_q64v3_kernel (d 64, <= 4 key tiles), attn_q64v2_kernel<64> (whole
 workgroups, key-split workgroups and both in one launch), attn_ws_kernel<128>, attn_q64v2_kernel<128> (key-split only) and the ws launch with a key-split
-tail behind it.  Which kernel a shape reaches depends on the CU count (kernel_refs.attn_route restates launch_attn_v2's rule); the case list is sized for
-256 CUs, tests/test_kernel_ref_teeth.py asserts there that it reaches every route in both element types.  Here the CU count is read from the device and the
-route printed per case; on another part the values are still checked and nothing is asserted about routes.
+tail behind it.  Which kernel a shape reaches depends on the CU count (kernel_refs.attn_route restates the dispatcher's rule, attn_plan; tests/
+test_kernel_ref_teeth.py compares the two over a sweep of shapes through fmx_attention_route); the case list is sized for 256 CUs, and that file asserts
+that it reaches every route in both element types.  Here the CU count is read from the device, the library's route for it must equal the restated one and
+is printed per case; on another part the values are still checked and nothing is asserted about which route a case was listed under.
 
-Out of scope (they stay on their knob tests in tests/test_gpu_kernels.py): attn_short_kernel, reachable only with a Q span >= 2 GB or FMX_ATTN_SHORT=1,
-and attn_q64_kernel<0>, which needs a K / V^T span >= 2 GB or FMX_ATTN_VARIANT=1.
+Spans that do not fit the 64-query kernels' 32-bit byte offsets (K / V^T of a (batch, head) >= 2e9 bytes, or Q under at most 128 keys) go to the generic
+32-query kernel, which addresses with 64-bit pointers: test_large_span_falls_back_to_the_generic_kernel.  The generic kernel's own cases (masks, causal,
+d_head 48 / 80 / 160, fewer than 256 queries) are tests/test_gpu_attention_generic.py.
 
 Reference: kernel_refs.attn_ref in fp64 on the rounded inputs, on the device in slices of <= 2^25 scores; every element within kernel_refs.ATTN_TOL; each
 check prints "[attention excess] <route> <layout> <case>: x.xxx".  Layouts are the executors' (backend/nn/unet.py self- and cross-attention, backend/nn/
@@ -278,6 +280,24 @@ def reference(bufs, L, dev=DEV, **plant):
 
 
 # ---- the GPU test ------------------------------------------------------------------------------------------------------------------------------------
+FAKE_PTR = 0x7F0000001000      # a 16-byte aligned non-null "device pointer" for fmx_attention_route, which dereferences nothing
+
+
+def library_route(lib, L, cus, **override):
+    """the route name the library's own dispatch plan gives a launch of layout L on `cus` compute units (fmx_attention_route: host only, no device)"""
+    from forge_amd import _lib
+    a = _lib.AttnArgs()
+    a.q = a.k = a.vt = a.o = a.zero_page = FAKE_PTR
+    a.batch, a.heads, a.nq, a.nk, a.nk_pad, a.dpad, a.scale = L.b, L.h, L.nq, L.nk, L.nk_pad, L.d, L.d ** -0.5
+    a.q_bs, a.q_rs, a.k_bs, a.k_rs, a.vt_bs, a.vt_hs, a.vt_ds = L.q_bs, L.q_rs, L.k_bs, L.k_rs, L.vt_bs, L.vt_hs, L.vt_ds
+    a.o_bs, a.o_rs = L.o_bs, L.o_rs or L.h * L.d
+    for k_, v_ in override.items():
+        setattr(a, k_, v_)
+    buf = C.create_string_buffer(64)
+    _lib.check(lib.fmx_attention_route(C.byref(a), cus, buf, len(buf)), "fmx_attention_route")
+    return buf.value.decode()
+
+
 def cu_count():
     from forge_amd import _lib
     cus = C.c_int(0)
@@ -306,6 +326,8 @@ def test_fast_attention(case, dtype):
     if cus == 256:
         assert route == case.route, f"{case.id}: reaches {route}, listed under {case.route}"
     L, bufs = build(case, dtype)
+    from forge_amd import _lib
+    assert library_route(_lib.lib(), L, cus) == route, f"{case.id}: kernel_refs.attn_route says {route}"
     want = reference(bufs, L)
     assert bool(torch.isfinite(want).all())
     got, o_after = launch(bufs, L)
@@ -314,3 +336,39 @@ def test_fast_attention(case, dtype):
     assert e <= 1.0, f"{case.id}: error {e:.3g}x ATTN_TOL[{dtype}] on {route}"
     if o_after is not None:
         assert window_violations(bufs["o"], o_after, L) == 0, f"{case.id}: the launch wrote outside its window of O"
+
+
+# ---- spans beyond 32-bit byte offsets ------------------------------------------------------------------------------------------------------------------
+# (name, nk, the stride that is stretched, its value in elements): b = h = 1, d 64, 256 queries.  The rows lie 2^24 (K) / 2^22 (Q) elements apart in a
+# buffer of ~2.1 GB that is allocated but, apart from those rows, never written or read.
+LARGE_SPAN = [("k_span", 64, "k_rs", 1 << 24),      # K rows 0 .. 63: 63 x 2^24 x 2 bytes >= 2e9
+              ("q_span", 77, "q_rs", 1 << 22)]      # Q rows 0 .. 255 under <= 128 keys (short2 reads Q through a descriptor): 255 x 2^22 x 2 bytes >= 2e9
+
+
+@pytest.mark.parametrize("dtype", DTS, ids=["f16", "bf16"])
+@pytest.mark.parametrize("name,nk,which,stride", LARGE_SPAN, ids=[c[0] for c in LARGE_SPAN])
+def test_large_span_falls_back_to_the_generic_kernel(name, nk, which, stride, dtype):
+    """a K / V^T / Q span that the 64-query kernels' 32-bit offsets cannot address runs on the generic kernel (64-bit addresses), within its ATTN_TOL"""
+    from forge_amd import _lib
+    nq, d = 256, 64
+    q, k, v = G.inputs(1, 1, nq, nk, d, dtype, seed=7700 + nk)
+    L = layout("dense", 1, 1, nq, nk, d)
+    setattr(L, which, stride)
+    assert ((L.nk_pad - 1) * L.k_rs + d) * 2 >= 2e9 or ((nq - 1) * L.q_rs + d) * 2 >= 2e9
+    cus = cu_count()
+    assert library_route(_lib.lib(), layout("dense", 1, 1, nq, nk, d), cus) == R.attn_route(1, 1, nq, nk, d, cus) != "generic"
+    assert library_route(_lib.lib(), L, cus) == "generic"
+    want = G.reference(q, k, v, nk, d)
+    rows = {"k_rs": k, "q_rs": q}[which][0, :, 0]
+    big = torch.empty((rows.shape[0] - 1) * stride + d, dtype=dtype, device=DEV)
+    torch.as_strided(big, tuple(rows.shape), (stride, 1)).copy_(rows)
+    dq, dk = (big, k.to(DEV)) if which == "q_rs" else (q.to(DEV), big)
+    vt = v.to(DEV).permute(2, 3, 0, 1).contiguous()
+    out = ops.attention(dq, dk, vt, batch=1, heads=1, nq=nq, nk=nk, nk_pad=L.nk_pad, dpad=d, scale=d ** -0.5, q_bs=L.q_bs, q_rs=L.q_rs, k_bs=L.k_bs,
+                        k_rs=L.k_rs, vt_bs=L.vt_bs, vt_hs=L.vt_hs, vt_ds=L.vt_ds)
+    torch.cuda.synchronize()
+    e = R.excess(out.view(1, nq, 1, d).permute(0, 2, 1, 3), want, dtype, *R.ATTN_TOL[dtype])
+    print(f"[attention excess] generic large-span {name} {'f16' if dtype == H16 else 'bf16'}: {e:.3f}")
+    del big, dq, dk
+    torch.cuda.empty_cache()
+    assert e <= 1.0, f"{name}: error {e:.3g}x ATTN_TOL[{dtype}] on the generic kernel"

@@ -772,9 +772,9 @@ def test_attention_d64_short_context_pipelined(nk, spikes):
 @pytest.mark.parametrize("b,h,nq,nk", [(16, 20, 1024, 77), (16, 10, 4096, 77), (1, 1, 4096, 77), (2, 3, 1000, 96), (2, 2, 300, 97), (1, 2, 2000, 128),
                                        (3, 5, 640, 32), (2, 2, 257, 65), (1, 7, 128 * 9 + 5, 31)])
 def test_attention_d64_short_context_persistent(b, h, nq, nk):
-    """Contexts of at most 128 keys on d_head 64 (every cross-attention against the 77-token text context) run attn_short_kernel (round 3): a
-    persistent workgroup walks several 128-query tiles of one (batch, head) with the K / V^T tiles staged once and the next tile's Q rows
-    requested ahead, a one-pass softmax over the 1-4 key blocks that hold keys.  Cases: the two bench shapes (3 and 6 tiles per workgroup, a
+    """Contexts of at most 128 keys on d_head 64 (every cross-attention against the 77-token text context) run attn_short2_kernel: a
+    persistent workgroup walks a range of the (batch, head, 128-query tile) list with the K / V^T tiles staged once per (batch, head) and the next
+    tile's Q rows requested ahead, a one-pass softmax over the 1-4 key blocks that hold keys.  Cases: the two bench shapes (3 and 6 tiles per workgroup, a
     short last chunk), one (batch, head) split over the whole chip, key counts on and next to every 32-key block edge, ragged query counts
     (a partial last tile, a partial last wave), padded keys holding garbage, a dominant key in the last valid position.  Against torch fp32
     and the 32-query kernel."""
@@ -837,7 +837,7 @@ def test_attention_fewer_keys_than_one_tile(d, nk):
 
 
 def test_attention_d64_generations_agree(monkeypatch):
-    """Second-generation d_head-64 kernel (default) against the first-generation one (the 32-query kernel reached through the test hook):
+    """The 64-query d_head-64 kernel (default) against the generic 32-query kernel (reached through the test hook):
     same inputs, results within fp16 rounding of each other on a 4096-token problem (Q pre-scaling and the deferred maximum change the
     rounding points, not the mathematics)."""
     b, h, n, d = 1, 2, 4096, 64

@@ -740,7 +740,8 @@ def test_fast_attention_cases_reach_every_route_at_256_cus():
 
 
 def test_attn_route_restates_the_dispatcher():
-    """spot values of the rule (csrc/fmx_attention.hip launch_attn_v2) at 256 and at 304 CUs"""
+    """spot values of the rule (csrc/fmx_attention.hip attn_plan) at 256 and at 304 CUs, then kernel_refs.attn_route against the library's own plan
+    (fmx_attention_route) over a sweep of shapes; masked, causal, forced-32 and large-span calls are "generic\""""
     assert R.attn_route(16, 20, 1024, 1024, 64, 256) == "q64v2<64> whole"         # 1280 entries = 2.5 rounds: 256 left, more than 3/8 of the slots
     assert R.attn_route(8, 20, 1024, 1024, 64, 256) == "q64v2<64> whole+split"    # 640 = 512 + 128
     assert R.attn_route(16, 10, 4096, 77, 64, 256) == "short2<3>"
@@ -749,6 +750,35 @@ def test_attn_route_restates_the_dispatcher():
     assert R.attn_route(1, 24, 1024, 1024, 128, 256) == "q64v2<128> split"
     assert R.attn_route(2, 3, 255, 77, 64, 256) == "generic" and R.attn_route(2, 3, 300, 77, 80, 256) == "generic"
     assert R.attn_route(2, 5, 52 * 256 - 37, 250, 64, 304) == "q64v3"              # 520 entries in one round of 608 slots, 520 > 3/8 of them: four whole tiles
+    # ... and the restatement against the dispatcher itself: fmx_attention_route runs the library's own plan function on the host
+    from forge_amd import _lib
+    try:
+        lib = _lib.lib()
+    except _lib.FmxError as e:
+        pytest.skip(f"libfmx not built: {e}")
+    checked = 0
+    for d in (48, 64, 80, 128, 160):
+        for nq in (255, 256, 257, 1000, 4096, 4352):
+            for nk in (1, 31, 32, 33, 64, 65, 77, 128, 129, 250, 256, 320, 1024, 4352):
+                for b, h in ((1, 1), (2, 3), (8, 20), (16, 20), (1, 24), (2, 24)):
+                    for cus in (256, 304):
+                        want = R.attn_route(b, h, nq, nk, d, cus)
+                        assert A.library_route(lib, A.layout("dense", b, h, nq, nk, d), cus) == want, (d, nq, nk, b, h, cus)
+                        checked += 1
+                    L = A.layout("dense", b, h, nq, nk, d)
+                    assert A.library_route(lib, L, 256, mask=A.FAKE_PTR, mask_qs=L.nk_pad) == "generic"
+                    assert A.library_route(lib, L, 256, scale=-(d ** -0.5)) == "generic"
+            L = A.layout("dense", 2, 3, nq, nq, d)
+            assert A.library_route(lib, L, 256, causal=1) == "generic"
+    assert checked == 5 * 6 * 14 * 6 * 2
+    # spans that do not fit 32-bit byte offsets: K rows 2^24 elements apart (63 x 2^25 bytes), Q rows 2^22 apart under at most 128 keys (255 x 2^23 bytes)
+    for d, nk in ((64, 64), (64, 1024), (128, 1024)):
+        L = A.layout("dense", 1, 1, 256, nk, d)
+        assert A.library_route(lib, L, 256) != "generic" and A.library_route(lib, L, 256, k_rs=1 << 24) == "generic"
+        assert A.library_route(lib, L, 256, vt_ds=1 << 24) == "generic" and A.library_route(lib, L, 256, k_rs=-L.k_rs) == "generic"
+    L = A.layout("dense", 1, 1, 256, 77, 64)
+    assert A.library_route(lib, L, 256) == "short2<3>" and A.library_route(lib, L, 256, q_rs=1 << 22) == "generic"
+    assert A.library_route(lib, A.layout("dense", 1, 1, 256, 129, 64), 256, q_rs=1 << 22) == "q64v3"     # the looped kernels read Q through 64-bit addresses
 
 
 @pytest.mark.parametrize("dtype", DTS)

@@ -18,6 +18,7 @@ ALLOWED = {
     "fmx_build_info": "build metadata, checked by tests/test_capi_symbols.py on the CPU",
     "fmx_active_knobs": "diagnostic string of the environment knobs, no arithmetic",
     "fmx_device_info": "device query, no kernel",
+    "fmx_attention_route": "host-only, no kernel: the dispatch plan by name, checked by tests/test_kernel_ref_teeth.py on the CPU",
     "fmx_graph_begin": "graph-capture helper for C callers; the Python side captures with torch.cuda.graph",
     "fmx_graph_end": "graph-capture helper for C callers; the Python side captures with torch.cuda.graph",
     "fmx_graph_launch": "graph-capture helper for C callers; the Python side captures with torch.cuda.graph",
