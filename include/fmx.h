@@ -48,6 +48,7 @@
  *   fmx_*_bf16             the bfloat16 build of the Flux path's kernels (last section)
  *   fmx_gguf_dequant_*     GGUF checkpoints: backend/utils.py:27-31 (load_torch_file), backend/operations_gguf.py (dequantize_tensor,
  *                          quants_mapping), backend/loader.py:181-211 (replace_state_dict), packages_3rdparty/gguf/quants.py (dequantize_blocks)
+ *   fmx_freeu_*            FreeU v2 extensions-builtin/sd_forge_freeu/scripts/forge_freeu.py:9-58 (Fourier_filter, output_block_patch)
  */
 #ifndef FMX_H
 #define FMX_H
@@ -550,6 +551,42 @@ int fmx_vae_sample_posterior_bf16(const void* moments, int32_t ld, const float* 
  * ---------------------------------------------------------------------------------------------- */
 int fmx_gguf_dequant_f16(int32_t qtype, const void* blocks, void* out, int64_t n_elements, void* stream);
 int fmx_gguf_dequant_bf16(int32_t qtype, const void* blocks, void* out, int64_t n_elements, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * FreeU v2 on the two inputs of a UNet output block (extensions-builtin/sd_forge_freeu/scripts/forge_freeu.py:9-58), in place, without an FFT.
+ * New symbols only: no existing signature moves, the ABI number stays 12.
+ *   h    : fp16 [n][hh*ww][c_h]  (channels-last), the backbone feature;   skip : fp16 [n][hh*ww][c_s], the skip feature
+ * backbone:  m[n,p] = mean over ALL c_h channels of h[n,p,:];  lo, hi = min, max of m[n,:] per sample;
+ *            h[n,p,c] *= (b - 1) * (m[n,p] - lo) / (hi - lo) + 1   for c < c_h / 2; the other channels are not written (bit for bit untouched).
+ *            hi == lo (a sample whose channel mean is the same at every pixel) is NOT special-cased: the reference divides by zero there and
+ *            so does this (the scaled half becomes NaN, or inf where the numerator is not zero).
+ * skip:      the reference scales, with threshold 1, the four frequency bins (0 | -1) x (0 | -1) of every plane by s and takes the real part of
+ *            the inverse transform.  Written out:  skip[n,p,c] += (s - 1) / (hh*ww) * sum_k S_k[n,c] * basis_k(p)  with the seven bases
+ *            1, cos tr, sin tr, cos tc, sin tc, cos(tr+tc), sin(tr+tc)  (tr = 2 pi row / hh, tc = 2 pi col / ww)  and
+ *            S_k[n,c] = sum over the pixels of skip[n,p,c] * basis_k(p).  Only defined for hh >= 2 and ww >= 2 (the reference's slice of bins
+ *            is empty when a side is 1).
+ * All arithmetic in fp32, every output element rounded to fp16 once.  No floating-point atomics: each workgroup of the reduce pass owns
+ * FMX_FREEU_CHUNK_PIXELS consecutive pixels of one sample and leaves its partial sums, which the apply pass adds in chunk order before it
+ * writes -- the same bits on every run.
+ *   trig      : fp32 [2*hh + 2*ww] = cos tr [hh] | sin tr [hh] | cos tc [ww] | sin tc [ww], computed by the caller (in double, rounded once);
+ *               cos(tr+tc) and sin(tr+tc) are formed from these in the kernels
+ *   nchunks   : must be ceil(hh*ww / FMX_FREEU_CHUNK_PIXELS)
+ *   workspace : fp32, at least FMX_FREEU_WORKSPACE_FLOATS(n, hh*ww, c_s, nchunks) values (workspace_floats says how many there are); written by
+ *               fmx_freeu_reduce_f16, read (and its tail written) by fmx_freeu_apply_f16, which must follow on the same stream with the same
+ *               geometry.  Layout: means [n*hw] | chunk min, max [n*nchunks*2] | partial sums [n][nchunks][7][c_s] | sums [n][7][c_s] |
+ *               lo, hi [n*2], every part starting at a multiple of 4 values.
+ * Requirements (FMX_E_BADARG otherwise, checked on the host before any launch): every pointer non-null and 16-byte aligned; n, hh, ww > 0;
+ * hh >= 2, ww >= 2; n <= 65535; c_h % 16 == 0; c_s % 8 == 0; nchunks and workspace_floats as above.
+ * ---------------------------------------------------------------------------------------------- */
+#define FMX_FREEU_CHUNK_PIXELS 256
+#define FMX_FREEU_PAD4(x) (((int64_t)(x) + 3) / 4 * 4)
+#define FMX_FREEU_WORKSPACE_FLOATS(n, hw, c_s, nchunks)                                                                          \
+  (FMX_FREEU_PAD4((int64_t)(n) * (hw)) + FMX_FREEU_PAD4((int64_t)(n) * (nchunks) * 2) + (int64_t)(n) * (nchunks) * 7 * (c_s) + \
+   (int64_t)(n) * 7 * (c_s) + FMX_FREEU_PAD4((int64_t)(n) * 2))
+int fmx_freeu_reduce_f16(const void* h, int32_t c_h, const void* skip, int32_t c_s, int32_t n, int32_t hh, int32_t ww, const float* trig,
+                         int32_t nchunks, float* workspace, int64_t workspace_floats, void* stream);
+int fmx_freeu_apply_f16(void* h, int32_t c_h, void* skip, int32_t c_s, int32_t n, int32_t hh, int32_t ww, const float* trig, int32_t nchunks,
+                        float* workspace, int64_t workspace_floats, float b, float s, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * HIP-graph helpers: capture everything launched on `stream` between begin/end into an executable graph.

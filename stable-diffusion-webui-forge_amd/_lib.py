@@ -167,6 +167,9 @@ SIGNATURES["fmx_taesd_pack_latent_bf16"] = SIGNATURES["fmx_taesd_pack_latent"]
 # GGUF block dequantisation at load time (qtype, blocks, out, n_elements, stream): new symbols, the ABI number does not move
 for _n in ("fmx_gguf_dequant_f16", "fmx_gguf_dequant_bf16"):
     SIGNATURES[_n] = [_i32, _vp, _vp, _i64, _vp]
+# native FreeU (h, c_h, skip, c_s, n, hh, ww, trig, nchunks, workspace, workspace_floats [, b, s], stream): new symbols, the ABI number does not move
+SIGNATURES["fmx_freeu_reduce_f16"] = [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _vp]
+SIGNATURES["fmx_freeu_apply_f16"] = [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _f32, _f32, _vp]
 
 
 def source_tree_hash():

@@ -29,6 +29,11 @@ def tensor_version(t):
         return -1
 
 
+def freeu_graph_key(freeu):
+    """what native FreeU adds to a graph key: ("freeu", b1, b2, s1, s2)"""
+    return ("freeu",) + tuple(float(v) for v in freeu[:4])
+
+
 def host_sigmas(sigma):
     info = getattr(sigma, "fmx_sigma", None)
     if info is not None:
@@ -81,8 +86,12 @@ class KModel:
             p = p.previous_controlnet
         return entries
 
-    def _forward_static(self, key, x, sigma_dev, sig_host, reps, ctxc, control=None, transformer_options=None, c_concat=None, control_plan=None):
-        """pack -> [ControlNets ->] UNet -> (returns eps view); static buffers per shape so the chain can be graph-replayed."""
+    def _forward_static(self, key, x, sigma_dev, sig_host, reps, ctxc, control=None, transformer_options=None, c_concat=None, control_plan=None,
+                        freeu=None):
+        """pack -> [ControlNets ->] UNet -> (returns eps view); static buffers per shape so the chain can be graph-replayed.
+        `freeu`: the job's native FreeU parameters (transformer_options["freeu_v2"], backend/patcher/freeu.py) or None.  They are launch
+        arguments of the captured kernels, so they are part of the graph key: the steps inside and outside the FreeU window of one job
+        are two graphs."""
         b, c, hh, ww = x.shape
         bu = reps * b
         st = self._static.get(key)
@@ -106,9 +115,11 @@ class KModel:
         concat_term = net.prepare_concat(c_concat, bu) if c_concat is not None else None  # cached per c_concat tensor: once per job
         if not self.use_graph or control is not None or hooks is not None:
             # Python hooks cannot be captured, and a ControlNet chain that needs Python per step arrives here with its residuals: eager
-            return net.forward_packed(st["xcol"], st["t"], ctxc, bu, hh, ww, control, hooks, concat_term)
+            return net.forward_packed(st["xcol"], st["t"], ctxc, bu, hh, ww, control, hooks, concat_term, freeu=freeu)
         active = [e for e in control_plan if e["active"]] if control_plan else []
         gkey = key if not active else key + ("control",) + tuple(e["cm"].exec_serial for e in active)
+        if freeu is not None:
+            gkey = gkey + freeu_graph_key(freeu)
 
         def run():
             # The ControlNet trunks read the SAME packed input and timestep buffers as the UNet (both are `calculate_input` of x and the
@@ -118,7 +129,7 @@ class KModel:
             for e in reversed(active):
                 outs = e["cm"].forward_static(st["xcol"], st["t"], e["ctxc"], bu, hh, ww, e["gh"])
                 ctrl = e["cn"].control_merge(None, outs, ctrl, torch.float32)
-            return net.forward_packed(st["xcol"], st["t"], ctxc, bu, hh, ww, control=ctrl, concat_term=concat_term)
+            return net.forward_packed(st["xcol"], st["t"], ctxc, bu, hh, ww, control=ctrl, concat_term=concat_term, freeu=freeu)
 
         def validity():
             # What a captured graph points at: the executors' arenas (re-allocated when a larger shape comes through, e.g. the hires pass),
@@ -177,6 +188,7 @@ class KModel:
         `transformer_options` with Python hooks: completed with the per-call keys of sampling_function.py:253-257 and run eagerly."""
         b, c, hh, ww = x.shape
         reps = 1 if uncond_ctx is None else 2
+        freeu = (transformer_options or {}).get("freeu_v2")   # native, no Python hook: stays on the graph path
         if self.diffusion_model._hooks(transformer_options) is not None or control_model is not None:
             to = dict(transformer_options or {})
             cond_or_uncond = [1, 0] if reps == 2 else [0]          # batch order [uncond ; cond] (sampling_function.py:187-229)
@@ -211,7 +223,7 @@ class KModel:
                 t_all.fmx_sigma = SigmaInfo(list(sig_host) * reps)
                 control = control_model.get_control(torch.cat([x] * reps), t_all, {"c_crossattn": ctx[0], "y": ctx[1]}, reps)
         eps = self._forward_static(key, x, sigma, sig_host, reps, ctxc, control=control, transformer_options=transformer_options, c_concat=c_concat,
-                                   control_plan=plan)
+                                   control_plan=plan, freeu=freeu)
         cond_pred = torch.empty_like(x) if want_parts else None
         uncond_pred = torch.empty_like(x) if want_parts else None
         den = ops.cfg_combine(eps, eps.shape[-1], x, sigma, reps, cond_scale, None, cond_pred, uncond_pred,
@@ -241,7 +253,8 @@ class KModel:
         sigma = t.to(device=self.device, dtype=torch.float32).contiguous()
         ctxc = self.diffusion_model.prepare_context(c_crossattn, y)
         b, c, hh, ww = x.shape
-        eps = self._forward_static((b, c, hh, ww, 1, "apply"), x, sigma, host_sigmas(t), 1, ctxc, control, transformer_options, c_concat)
+        eps = self._forward_static((b, c, hh, ww, 1, "apply"), x, sigma, host_sigmas(t), 1, ctxc, control, transformer_options, c_concat,
+                                   freeu=(transformer_options or {}).get("freeu_v2"))
         return ops.cfg_combine(eps, eps.shape[-1], x, sigma, 1, 1.0, prediction_type=self.predictor.prediction_type,
                                sigma_data=self.predictor.sigma_data)
 
@@ -263,6 +276,8 @@ class KModelFlux:
         return 0
 
     def apply_model(self, x, t, c_concat=None, c_crossattn=None, control=None, transformer_options=None, y=None, guidance=None, **kwargs):
+        if (transformer_options or {}).get("freeu_v2") is not None:
+            raise NotImplementedError("FreeU: UNet models only")   # the reference's script declines models without model_channels
         if c_concat is not None or control is not None:
             raise NotImplementedError("c_concat / control are outside the txt2img hot path")
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
@@ -275,6 +290,8 @@ class KModelFlux:
 
     def denoise_cfg(self, x, sigma, uncond_ctx, cond_ctx, cond_scale, want_parts=False, transformer_options=None, control_model=None):
         to = transformer_options or {}
+        if to.get("freeu_v2") is not None:
+            raise NotImplementedError("FreeU: UNet models only")
         if control_model is not None or to.get("patches") or to.get("patches_replace") or to.get("block_modifiers"):
             raise NotImplementedError("ControlNet / per-block hooks are built for the LDM UNet executor, not for the Flux transformer")
         ctx, y, guidance = cond_ctx

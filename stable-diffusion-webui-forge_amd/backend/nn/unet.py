@@ -708,9 +708,18 @@ class IntegratedUNet2DConditionModel:
         self._concat_cache = (key, term, c_concat)
         return term
 
-    def _forward_impl(self, xcol, t, ctxc, bu, hh, ww, arena, control=None, to=None, concat_term=None):
+    def _forward_impl(self, xcol, t, ctxc, bu, hh, ww, arena, control=None, to=None, concat_term=None, freeu=None):
         """xcol: [Bu*H*W, 64] im2col of the (scaled) input; t: [Bu] fp32 table indices.  -> eps [Bu*H*W, out_ch].
-        `to`: transformer_options with Python hooks (unet.py:696-763 hook points), or None on the fast path."""
+        `to`: transformer_options with Python hooks (unet.py:696-763 hook points), or None on the fast path.
+        `freeu`: a FreeUParams tuple (b1, b2, s1, s2, ...) of backend/patcher/freeu.py, or None: native FreeU v2 on the inputs of the
+        output blocks whose h has 4x / 2x model_channels channels.  Not a Python hook: it runs on the fast path and inside a captured graph.  It
+        runs where the reference's output_block_patch runs when FreeU is the first installed patch; a job that ALSO installs Python
+        output-block patches gets native FreeU first, then those patches, eagerly as before."""
+        freeu_scales = None
+        if freeu is not None:
+            b1, b2, s1, s2 = (float(v) for v in freeu[:4])
+            mc = self.layout.model_channels
+            freeu_scales = {4 * mc: (b1, s1), 2 * mc: (b2, s2)}
         if control is not None:
             control = {k: list(v) for k, v in control.items()}
         lay = self.layout
@@ -777,6 +786,13 @@ class IntegratedUNet2DConditionModel:
             if to is not None:
                 to["block"] = ("output", bi)
             skip = self._apply_control(hs.pop(), control, "output")
+            scale = freeu_scales.get(h.shape[-1]) if freeu_scales is not None else None
+            if scale is not None:
+                mk = arena.mark()
+                ops.freeu(h, skip, *scale)       # in place; the scratch goes back to the arena
+                arena.release(mk)
+                self._tap(f"output.{bi}.freeu.h", h)
+                self._tap(f"output.{bi}.freeu.skip", skip)
             for p in patches.get("output_block_patch", []):
                 hv, sv = h.permute(0, 3, 1, 2), skip.permute(0, 3, 1, 2)
                 ops.clear_stats(h)
@@ -829,15 +845,15 @@ class IntegratedUNet2DConditionModel:
             self.arena_epoch += 1
         return self._arena
 
-    def forward_packed(self, xcol, t, ctxc, bu, hh, ww, control=None, transformer_options=None, concat_term=None):
+    def forward_packed(self, xcol, t, ctxc, bu, hh, ww, control=None, transformer_options=None, concat_term=None, freeu=None):
         """Hot-path entry (no layout conversion): returns eps as fp16 [Bu*H*W, out_channels] living in the arena
-        (valid until the next forward)."""
+        (valid until the next forward).  `freeu`: see _forward_impl (the caller takes it out of transformer_options["freeu_v2"])."""
         while True:
             arena = self._get_arena(bu, hh, ww)
             arena.reset()
             try:
                 with arena:
-                    return self._forward_impl(xcol, t, ctxc, bu, hh, ww, arena, control, self._hooks(transformer_options), concat_term)
+                    return self._forward_impl(xcol, t, ctxc, bu, hh, ww, arena, control, self._hooks(transformer_options), concat_term, freeu)
             except ArenaOverflow:
                 torch.cuda.synchronize(self.device)
                 self._arena_bytes = arena.capacity * 2
@@ -875,7 +891,7 @@ class IntegratedUNet2DConditionModel:
             x = x[:, :self.latent_channels]
         xcol = ops.unet_pack_input(x.contiguous(), ones, 1, 1.0)
         eps = self.forward_packed(xcol, timesteps.to(device=self.device, dtype=torch.float32).contiguous(), ctxc, bu, hh, ww, control,
-                                  transformer_options, concat_term)
+                                  transformer_options, concat_term, freeu=(transformer_options or {}).get("freeu_v2"))
         return eps.view(bu, hh, ww, -1).permute(0, 3, 1, 2).to(x.dtype)
 
     __call__ = forward

@@ -270,6 +270,10 @@ def sampling_function(self, denoiser_params, cond_scale, cond_composition):
             for h in uncond:
                 h["control"] = control
     model_options, seed = unet_patcher.model_options, self.p.seeds[0]
+    if model_options.get("transformer_options", {}).get("freeu_v2") is not None:
+        # native FreeU (backend/patcher/freeu.py): the reference's on_cfg_denoiser callback switches the patch off outside its step window
+        from ..patcher.freeu import options_for_step
+        model_options = options_for_step(model_options, denoiser_params.sampling_step, denoiser_params.total_sampling_steps)
     for modifier in model_options.get("conditioning_modifiers", []):  # :359-360
         model, x, timestep, uncond, cond, cond_scale, model_options, seed = modifier(model, x, timestep, uncond, cond, cond_scale, model_options, seed)
     return sampling_function_inner(model, x, timestep, uncond, cond, cond_scale, model_options, seed, return_full=True)

@@ -596,6 +596,55 @@ def add_control_(h, ctrl, alpha=1.0):
     return h
 
 
+FREEU_CHUNK_PIXELS = 256      # FMX_FREEU_CHUNK_PIXELS of include/fmx.h
+_freeu_trig = {}
+
+
+def freeu_geometry(n, hw, c_s):
+    """-> (pixel chunks per sample, fp32 values of workspace): FMX_FREEU_WORKSPACE_FLOATS of include/fmx.h, which the library checks again"""
+    nchunks = -(-hw // FREEU_CHUNK_PIXELS)
+    pad4 = lambda v: (v + 3) // 4 * 4  # noqa: E731
+    return nchunks, pad4(n * hw) + pad4(n * nchunks * 2) + n * nchunks * 7 * c_s + n * 7 * c_s + pad4(n * 2)
+
+
+def freeu_trig_table(hh, ww, device):
+    """fp32 [2*hh + 2*ww] = cos | sin of 2 pi row / hh, cos | sin of 2 pi col / ww: computed in double on the host, rounded once, kept per
+    (hh, ww, device) for the life of the process (a captured graph keeps its address)."""
+    key = (hh, ww, device.type, device.index)
+    t = _freeu_trig.get(key)
+    if t is None:
+        import math
+        tr = [2.0 * math.pi * r / hh for r in range(hh)]
+        tc = [2.0 * math.pi * c / ww for c in range(ww)]
+        host = torch.tensor([math.cos(a) for a in tr] + [math.sin(a) for a in tr] + [math.cos(a) for a in tc] + [math.sin(a) for a in tc],
+                            dtype=torch.float64).to(torch.float32)
+        t = _freeu_trig[key] = host.to(device)
+    return t
+
+
+def freeu(h, skip, b, s):
+    """FreeU v2 on the inputs of one output block, in place (include/fmx.h, section "FreeU v2"): h [N, H, W, C_h] fp16 NHWC -- its first C_h / 2
+    channels times (b - 1) * normalised channel mean + 1 --, skip [N, H, W, C_s] -- its four lowest frequency bins per plane times s.
+    -> (h, skip), the same tensors.  GroupNorm statistics their producers attached are stale afterwards and are dropped."""
+    if h.dim() != 4 or skip.dim() != 4 or tuple(h.shape[:3]) != tuple(skip.shape[:3]) or not h.is_contiguous() or not skip.is_contiguous():
+        raise ValueError(f"freeu expects contiguous NHWC tensors of one n, H, W: got {tuple(h.shape)} and {tuple(skip.shape)}")
+    n, hh, ww, c_h = h.shape
+    c_s = skip.shape[-1]
+    if hh < 2 or ww < 2:
+        raise ValueError(f"freeu: the Fourier filter is defined for H >= 2 and W >= 2 only, got {hh} x {ww}")
+    _check_f16(h, skip)
+    nchunks, ws_floats = freeu_geometry(n, hh * ww, c_s)
+    trig = freeu_trig_table(hh, ww, h.device)
+    ws = empty((ws_floats,), torch.float32, h.device)
+    clear_stats(h)
+    clear_stats(skip)
+    L = _lib.lib()
+    _lib.check(L.fmx_freeu_reduce_f16(_p(h), c_h, _p(skip), c_s, n, hh, ww, _p(trig), nchunks, _p(ws), ws_floats, stream_ptr()), "fmx_freeu_reduce_f16")
+    _lib.check(L.fmx_freeu_apply_f16(_p(h), c_h, _p(skip), c_s, n, hh, ww, _p(trig), nchunks, _p(ws), ws_floats, float(b), float(s), stream_ptr()),
+               "fmx_freeu_apply_f16")
+    return h, skip
+
+
 ACT_QUICK_GELU, ACT_GELU_ERF, ACT_RELU = 0, 1, 2
 
 

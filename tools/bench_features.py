@@ -1,9 +1,10 @@
 #!/usr/bin/env python
 """Full-size (SDXL 1024x1024, batch 8, fp16, CFG 7) timings of the widened paths, one JSON line each: every sampler family, ControlNet,
-per-block hooks (eager path), AND-composed prompts, hires-fix second pass.  Not the headline bench (bench.py): this is the check that the
-§8f rows hold up at the BASELINE shape -- arena sizing, 32-bit offsets, graph capture with other batch sizes -- and what they cost.
+per-block hooks (eager path), FreeU (plain / native / hooked, interleaved), AND-composed prompts, hires-fix second pass.  Not the headline
+bench (bench.py): this is the check that the §8f rows hold up at the BASELINE shape -- arena sizing, 32-bit offsets, graph capture with other
+batch sizes -- and what they cost.
 
-    python tools/bench_features.py [--steps 6] [--only samplers,controlnet,hooks,and,hires]
+    python tools/bench_features.py [--steps 6] [--only samplers,controlnet,hooks,freeu,and,hires]
     python tools/bench_features.py --only taesd      the TAESD decode of batch x (res/8)^2 SDXL-shaped latents (synthetic weights, fp16) next to the Full
                                                      VAE decode of the same latents in the same process: median of 5 after warm-up, events around the calls
 """
@@ -67,7 +68,7 @@ def main():
     ap.add_argument("--res", type=int, default=1024)
     ap.add_argument("--width", type=int, default=0)
     ap.add_argument("--height", type=int, default=0)
-    ap.add_argument("--only", default="samplers,controlnet,hooks,and,hires")
+    ap.add_argument("--only", default="samplers,controlnet,hooks,freeu,and,hires")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     width, height = a.width or a.res, a.height or a.res
@@ -107,8 +108,81 @@ def main():
         print(json.dumps({"case": label, "sampler": sampler, "steps": steps, "ms_per_step": round(dt / steps * 1e3, 2),
                           "ms_total": round(dt * 1e3, 1), "finite": ok, "shape": list(lat.shape)}), flush=True)
 
+    def freeu_leg(rounds=5, preset="SDXL"):
+        """Plain, native FreeU (transformer option, captured graph) and hooked FreeU (the same arithmetic as a Python output_block_patch:
+        tests/freeu_refs.py's closed form in torch fp32, so no FFT library either; eager) -- primed once each, then timed alternately, `rounds`
+        windows of a.steps steps per variant, in this one process.  Also the FreeU launches of one UNet call on their own (device events,
+        median of 20), which is what the native route adds to a step."""
+        import freeu_refs as fr
+        from forge_amd import hipops as ops
+        from forge_amd.backend.patcher import freeu as pf
+        p = pf.PRESETS[preset]
+        mc = cfg["model_channels"]
+        scales = {4 * mc: (p.b1, p.s1), 2 * mc: (p.b2, p.s2)}
+
+        def patch(h, hsp, to):
+            sc = scales.get(h.shape[1])
+            return (h, hsp) if sc is None else fr.freeu_ref(h, hsp, *sc, dtype=torch.float32)
+        hooked = eng.forge_objects.unet.clone()
+        hooked.set_model_output_block_patch(patch)
+        variants = {"plain": None, "freeu_native": pf.patch_freeu_v2(eng.forge_objects.unet, *p), "freeu_hooked": hooked}
+        shapes = []                       # (n, hh, ww, c_h, c_s) of every ops.freeu call of one UNet call
+        real = ops.freeu
+        ops.freeu = lambda h, s, *r: (shapes.append((*h.shape, s.shape[-1])), real(h, s, *r))[1]
+        saved = eng.forge_objects_after_applying_lora
+
+        def once(unet, n):
+            if unet is not None:
+                eng.forge_objects_after_applying_lora = saved.shallow_copy()
+                eng.forge_objects_after_applying_lora.unet = unet
+            try:
+                pr = processing.StableDiffusionProcessingTxt2Img(sd_model=eng, c=c1, uc=u1, seed=1, sampler_name="Euler", batch_size=b, steps=n,
+                                                                 cfg_scale=7.0, width=width, height=height, do_decode=False)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                lat = processing.process_images(pr).latents
+                torch.cuda.synchronize()
+                return time.perf_counter() - t0, lat
+            finally:
+                eng.forge_objects_after_applying_lora = saved
+                eng.forge_objects = saved.shallow_copy()
+        try:
+            for unet in variants.values():    # priming (arena, caches, graphs)
+                once(unet, 4)
+        finally:
+            ops.freeu = real
+        stop = next((i for i in range(1, len(shapes)) if shapes[i][1] < shapes[i - 1][1]), len(shapes))   # the resolution only grows within one call
+        per_call = shapes[:stop]
+        ms = {k: [] for k in variants}
+        finite = True
+        for _ in range(rounds):
+            for k, unet in variants.items():
+                dt, lat = once(unet, a.steps)
+                ms[k].append(round(dt / a.steps * 1e3, 2))
+                finite = finite and bool(torch.isfinite(lat).all())
+        med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+        # the kernels alone, on tensors of the shapes the UNet call passed
+        bufs = [(torch.randn(s[:4], device=dev).half(), torch.randn(*s[:3], s[4], device=dev).half(), *scales[s[3]]) for s in per_call]
+        kern = []
+        for i in range(23):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for args in bufs:
+                ops.freeu(*args)
+            e1.record()
+            torch.cuda.synchronize()
+            if i >= 3:
+                kern.append(e0.elapsed_time(e1))
+        print(json.dumps({"case": f"FreeU ({preset} preset): plain vs native (captured graph) vs hooked (Python output_block_patch, eager)", "sampler": "Euler",
+                          "steps": a.steps, "rounds": rounds, "ms_per_step": med, "ms_per_step_rounds": ms,
+                          "native_minus_plain_ms": round(med["freeu_native"] - med["plain"], 2),
+                          "freeu_calls_per_unet_call": [list(s) for s in per_call], "freeu_kernels_ms_per_unet_call": round(sorted(kern)[len(kern) // 2], 3),
+                          "finite": finite, "shape": list(lat.shape)}), flush=True)
+
     if "one" in what:
         run(f"{width}x{height}", sampler="Euler")
+    if "freeu" in what:
+        freeu_leg()
     if "samplers" in what:
         for s in ("Euler", "Euler a", "DPM++ 2M", "Heun", "DPM2 a", "DPM++ 2S a", "LMS", "IPNDM_V", "DEIS", "DPM++ SDE", "DPM++ 2M SDE", "DPM++ 3M SDE",
                   "DPM fast", "DDIM", "PLMS", "UniPC", "LCM", "DDPM"):
