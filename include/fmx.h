@@ -48,6 +48,9 @@
  *   fmx_*_bf16             the bfloat16 build of the Flux path's kernels (last section)
  *   fmx_gguf_dequant_*     GGUF checkpoints: backend/utils.py:27-31 (load_torch_file), backend/operations_gguf.py (dequantize_tensor,
  *                          quants_mapping), backend/loader.py:181-211 (replace_state_dict), packages_3rdparty/gguf/quants.py (dequantize_blocks)
+ *   fmx_fp8_expand_*,      float8 and bitsandbytes NF4 / FP4 checkpoint storage: backend/loader.py:81-174 (storage type per component),
+ *   fmx_bnb4_dequant_*     backend/memory_management.py:311-337 (state_dict_dtype), backend/operations_bnb.py (ForgeParams4bit, functional_linear_4bits),
+ *                          backend/operations.py:353-389 (the manual cast of fp8-stored weights)
  *   fmx_freeu_*            FreeU v2 extensions-builtin/sd_forge_freeu/scripts/forge_freeu.py:9-58 (Fourier_filter, output_block_patch)
  */
 #ifndef FMX_H
@@ -551,6 +554,37 @@ int fmx_vae_sample_posterior_bf16(const void* moments, int32_t ld, const float* 
  * ---------------------------------------------------------------------------------------------- */
 int fmx_gguf_dequant_f16(int32_t qtype, const void* blocks, void* out, int64_t n_elements, void* stream);
 int fmx_gguf_dequant_bf16(int32_t qtype, const void* blocks, void* out, int64_t n_elements, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * float8 and bitsandbytes 4-bit checkpoint storage: packed bytes -> the 16-bit resident weights the executors consume, once, at load time, as for
+ * GGUF (the reference keeps fp8 weights and casts them in every forward, backend/operations.py:353-389, and keeps bnb weights packed and calls
+ * the library's dequantiser in every forward, backend/operations_bnb.py; which tensors are stored how is decided per component by
+ * backend/memory_management.py:311-337 and backend/loader.py:81-174).  New symbols only: no existing signature moves, the ABI number stays 12.
+ *
+ * fmx_fp8_expand_*: n codes at `src` (8-byte aligned) -> n 16-bit values at `out` (16-byte aligned).
+ *   kind       : 0 float8_e4m3fn (OCP: no infinities; codes 0x7F and 0xFF are NaN), 1 float8_e5m2.  Any other kind (the fnuz variants included)
+ *                returns FMX_E_UNSUPPORTED.
+ * All four expansions are exact (every code of both kinds is representable in fp16 and in bf16): torch's CPU `.to()` bit for bit.  NaN codes
+ * become a quiet NaN; infinities (e5m2) and signed zeros are kept.  Decoded with bit arithmetic, no hardware fp8 conversion is involved.
+ *
+ * fmx_bnb4_dequant_*: the tensor format of bitsandbytes' QuantState.as_dict(packed=True), one launch per tensor, no intermediate absmax tensor.
+ *   packed     : (n + 1) / 2 bytes, 16-byte aligned.  Weight i is in byte i >> 1: an even i is the HIGH nibble, an odd i the low one; for an odd n
+ *                the low nibble of the last byte is unused.
+ *   code16     : 16 fp32 values, the file's quant_map (NF4 or FP4: the kernel holds no table of its own).
+ *   absmax_f32 : flat form: one fp32 scale per block of `blocksize` weights.  NULL in the nested form.
+ *   absmax_u8, code256, absmax2, offset, blocksize2 : nested form: the scale of block b is  code256[absmax_u8[b]] * absmax2[b / blocksize2] + offset,
+ *                one fp32 multiply followed by one fp32 add, each rounded (no FMA).  NULL / 0 in the flat form.
+ *   blocksize  : a power of two from 64 to 4096;  blocksize2 : a power of two of at least 64.
+ * value(i) = code16[nibble] * scale in ONE fp32 multiply, rounded once, to nearest even, to the output type (beyond the fp16 range: inf, as torch's
+ * cast).  FMX_E_BADARG before any launch for a null required pointer, n <= 0, a bad block size, both absmax forms or neither, `packed` or `out`
+ * not 16-byte aligned.  Parity of format and arithmetic is UNPINNED against bitsandbytes itself: the reference only calls it.
+ * ---------------------------------------------------------------------------------------------- */
+int fmx_fp8_expand_f16(int32_t kind, const void* src, void* out, int64_t n, void* stream);
+int fmx_fp8_expand_bf16(int32_t kind, const void* src, void* out, int64_t n, void* stream);
+int fmx_bnb4_dequant_f16(const void* packed, const float* code16, const float* absmax_f32, const uint8_t* absmax_u8, const float* code256,
+                         const float* absmax2, float offset, int32_t blocksize2, int32_t blocksize, void* out, int64_t n, void* stream);
+int fmx_bnb4_dequant_bf16(const void* packed, const float* code16, const float* absmax_f32, const uint8_t* absmax_u8, const float* code256,
+                          const float* absmax2, float offset, int32_t blocksize2, int32_t blocksize, void* out, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * FreeU v2 on the two inputs of a UNet output block (extensions-builtin/sd_forge_freeu/scripts/forge_freeu.py:9-58), in place, without an FFT.

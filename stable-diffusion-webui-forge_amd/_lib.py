@@ -167,6 +167,11 @@ SIGNATURES["fmx_taesd_pack_latent_bf16"] = SIGNATURES["fmx_taesd_pack_latent"]
 # GGUF block dequantisation at load time (qtype, blocks, out, n_elements, stream): new symbols, the ABI number does not move
 for _n in ("fmx_gguf_dequant_f16", "fmx_gguf_dequant_bf16"):
     SIGNATURES[_n] = [_i32, _vp, _vp, _i64, _vp]
+# float8 / bitsandbytes 4-bit checkpoint storage, expanded at load time: new symbols, the ABI number does not move
+for _n in ("fmx_fp8_expand_f16", "fmx_fp8_expand_bf16"):       # (kind, src, out, n, stream)
+    SIGNATURES[_n] = [_i32, _vp, _vp, _i64, _vp]
+for _n in ("fmx_bnb4_dequant_f16", "fmx_bnb4_dequant_bf16"):   # (packed, code16, absmax_f32, absmax_u8, code256, absmax2, offset, blocksize2, blocksize, out, n, stream)
+    SIGNATURES[_n] = [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _vp, _i64, _vp]
 # native FreeU (h, c_h, skip, c_s, n, hh, ww, trig, nchunks, workspace, workspace_floats [, b, s], stream): new symbols, the ABI number does not move
 SIGNATURES["fmx_freeu_reduce_f16"] = [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _vp]
 SIGNATURES["fmx_freeu_apply_f16"] = [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _f32, _f32, _vp]

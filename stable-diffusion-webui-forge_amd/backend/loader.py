@@ -39,10 +39,40 @@ def _is_gguf(v):
     return isinstance(v, GGUFTensor)
 
 
+def _is_packed(v):
+    """a tensor the device expands: a GGUFTensor, or a PackedTensor (float8 / bitsandbytes 4-bit storage, backend/quant_state.py)"""
+    from .quant_state import PackedTensor
+    return _is_gguf(v) or isinstance(v, PackedTensor)
+
+
+def _staged_parts(v):
+    """-> [(name, flat uint8 host view)] of what one packed tensor sends to the device: its bytes, and for a bitsandbytes tensor its small side
+    tensors (absmax and the tables) behind them.  Views only: nothing is copied here."""
+    if _is_gguf(v):
+        return [("data", v.data)]
+    parts = [("data", v.data.numpy())]
+    if v.state is not None:
+        parts += [(name, t.view(torch.uint8).numpy()) for name in ("absmax", "code", "code2", "absmax2") for t in (getattr(v.state, name),) if t is not None]
+    return parts
+
+
+def _staged_layout(parts):
+    """-> ([(name, offset, view)], total) for the parts of one tensor: every part at a 16-byte aligned offset of one staging segment; a tensor
+    without side tensors takes exactly its own bytes"""
+    layout, off, end = [], 0, 0
+    for name, a in parts:
+        layout.append((name, off, a))
+        end = off + a.nbytes
+        off = (end + 15) // 16 * 16
+    return layout, end
+
+
 @torch.inference_mode()
 def dequantize_state_dict(sd, device="cuda", dtype=torch.bfloat16):
     """Materialise a state dict read from a GGUF file: every GGUFTensor is copied to the device as packed bytes and expanded there into a `dtype`
-    (fp16 / bf16) tensor of its shape by the fmx_gguf_dequant kernels; ordinary tensors pass through untouched.  The reference keeps the blocks and
+    (fp16 / bf16) tensor of its shape by the fmx_gguf_dequant kernels; ordinary tensors pass through untouched.  PackedTensor values (float8 and
+    bitsandbytes NF4 / FP4 storage, backend/quant_state.py) take the same route through fmx_fp8_expand / fmx_bnb4_dequant; a bitsandbytes
+    tensor's side tensors (absmax, tables) are staged behind its bytes, in the same copy.  The reference keeps the blocks and
     dequantises inside every forward (operations_gguf.py); here the weights become the resident 16-bit tensors the executors consume, once.
 
     Staging: two pinned host buffers of the largest tensor's packed size, used alternately, and one side stream.  Tensor i+1 is copied into its
@@ -50,40 +80,50 @@ def dequantize_state_dict(sd, device="cuda", dtype=torch.bfloat16):
     copy is still in flight.  The packed device copy is freed to the stream-ordered allocator as soon as its kernel is queued, so the extra device
     memory at any time is a couple of tensors' packed bytes, not the file's."""
     from .. import hipops
-    if not any(_is_gguf(v) for v in sd.values()):
+    if not any(_is_packed(v) for v in sd.values()):
         return sd
     # F32 / F16 / BF16 tensors of the file (norm scales, biases, tables) are ordinary tensors of their own type, as the reference keeps them:
     # consumers that want fp32 (the T5 bias table) get every stored bit; the executors cast the rest when they bind them
     plain = {0: torch.float32, 1: torch.float16, 30: torch.bfloat16}
     sd = {k: (torch.from_numpy(v.data.copy()).view(plain[v.qtype]).reshape(v.shape) if _is_gguf(v) and v.qtype in plain else v) for k, v in sd.items()}
-    todo = [(k, v) for k, v in sd.items() if _is_gguf(v)]
+    todo = [(k, v, *_staged_layout(_staged_parts(v))) for k, v in sd.items() if _is_packed(v)]      # views and offsets: no bytes are read yet
     if not todo:
         return sd
     device = torch.device(device)
     if device.type != "cuda":
-        raise ValueError("GGUF tensors are dequantised on the GPU: device must be a cuda device")
+        raise ValueError("GGUF, float8 and bitsandbytes tensors are expanded on the GPU: device must be a cuda device")
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
     out = dict(sd)
-    cap = max(v.data.nbytes for _, v in todo)
+    cap = max(n for _, _, _, n in todo)
     pinned = [torch.empty(cap, dtype=torch.uint8).pin_memory() for _ in range(2)]
     free = [None, None]                 # event: the buffer's last host-to-device copy has completed
     with torch.cuda.device(device):
         stream = torch.cuda.Stream(device)
         stream.wait_stream(torch.cuda.current_stream(device))
         with torch.cuda.stream(stream):
-            for i, (k, v) in enumerate(todo):
-                n = v.data.nbytes
+            for i, (k, v, layout, n) in enumerate(todo):
                 slot = i & 1
                 if free[slot] is not None:
                     free[slot].synchronize()
                 stage = pinned[slot][:n]
-                stage.numpy()[:] = v.data                                   # page-in + copy from the mapping: the file read
+                for _, off, a in layout:
+                    stage.numpy()[off:off + a.nbytes] = a                   # page-in + copy from the mapping: the file read
                 raw = torch.empty(n, dtype=torch.uint8, device=device)
                 raw.copy_(stage, non_blocking=True)
                 free[slot] = torch.cuda.Event()
                 free[slot].record(stream)
-                out[k] = hipops.gguf_dequant(raw, v.qtype, v.shape, dtype)
+                if _is_gguf(v):
+                    out[k] = hipops.gguf_dequant(raw, v.qtype, v.shape, dtype)
+                elif v.state is None:
+                    out[k] = hipops.fp8_expand(raw, v.scheme, v.shape, dtype)
+                else:
+                    dev = {name: raw[off:off + a.nbytes] for name, off, a in layout}
+                    f32 = lambda t: t.view(torch.float32) if t is not None else None  # noqa: E731
+                    state = v.state._replace(code=f32(dev["code"]), absmax=dev["absmax"] if v.state.nested else f32(dev["absmax"]),
+                                             code2=f32(dev.get("code2")), absmax2=f32(dev.get("absmax2")))
+                    out[k] = hipops.bnb4_dequant(dev["data"], state, dtype)
+                    del dev, state
                 del raw                                                     # allocated and freed on this stream: reusable by the next tensor
         torch.cuda.current_stream(device).wait_stream(stream)
         stream.synchronize()
@@ -217,6 +257,20 @@ def detect_vae_config(vae_sd, **constants):
                 use_quant_conv="quant_conv.weight" in vae_sd, use_post_quant_conv="post_quant_conv.weight" in vae_sd, **constants)
 
 
+def _vae_as_stored(vae, prefix):
+    """VAEs stay as stored: the reference builds the VAE in its own type whatever the file's, so a float8 tensor is only cast (here: to its exact
+    fp32 values, on the host, before any key conversion touches it); a bitsandbytes tensor has no meaning there and is refused by key."""
+    from .quant_state import is_packed
+    out = {}
+    for k, v in vae.items():
+        if is_packed(v):
+            if not v.is_fp8:
+                raise NotImplementedError(f"{prefix}{k}: bitsandbytes {v.scheme} storage is not served for a VAE")
+            v = v.host_float()
+        out[k] = v
+    return out
+
+
 def flux_prefix(sd):
     """-> key prefix of a Flux transformer inside `sd` ('model.diffusion_model.' in full checkpoints, '' in transformer-only files), or None."""
     for prefix in (UNET_PREFIX, ""):
@@ -247,8 +301,9 @@ FLUX_VAE_PREFIXES = ("vae.", VAE_PREFIX)  # Forge's own Flux checkpoints store t
 
 def split_flux_state_dict(sd):
     """Flux counterpart of split_state_dict: -> ({'transformer', 'vae'}, guess).  The compute type follows the stored tensors as the reference's
-    loader does (bf16 files -> bf16, fp16 files -> fp16; fp32 files run in bf16, the reference's first choice for Flux); GGUF files -> bf16);
-    fp8 / nf4 / fp4 storage is outside the native path.  Shapes are all that is read here, so GGUF tensors need no dequantisation yet."""
+    loader does (bf16 files -> bf16, fp16 files -> fp16; fp32 files run in bf16, the reference's first choice for Flux; GGUF files and wrapped
+    float8 / bitsandbytes nf4 / fp4 files (quant_state.wrap_quantized_state_dict, applied by forge_loader) -> bf16).  Raw float8 tensors are
+    refused: only wrapped ones are accepted.  Shapes are all that is read here, so packed tensors need no expansion yet."""
     prefix = flux_prefix(sd)
     tr = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix) and not k.startswith(FLUX_VAE_PREFIXES + ("text_encoders.",))}
     vae = {}
@@ -256,13 +311,14 @@ def split_flux_state_dict(sd):
     for vp in FLUX_VAE_PREFIXES:
         vae = {k[len(vp):]: v for k, v in sd.items() if k.startswith(vp)}
         if vae:
-            vae = vae_from_diffusers(vae)
+            vae = vae_from_diffusers(_vae_as_stored(vae, vp))
             break
     probe = tr["img_in.weight"]
     # a GGUF file runs in bf16, the reference's first choice for Flux; its tensors are expanded by dequantize_state_dict
-    stored = torch.bfloat16 if _is_gguf(probe) else probe.dtype
+    stored = torch.bfloat16 if _is_packed(probe) else probe.dtype
     if stored not in (torch.float16, torch.bfloat16, torch.float32):
-        raise NotImplementedError(f"Flux checkpoint stored as {stored}: fp8 and bitsandbytes nf4 / fp4 storage are not on the native path")
+        raise NotImplementedError(f"Flux state dict holds raw {stored} tensors: float8 and bitsandbytes nf4 / fp4 storage is loaded through forge_loader, "
+                                  "which wraps such tensors first (quant_state.wrap_quantized_state_dict)")
     guess = {"flux_config": detect_flux_config(sd, prefix), "vae_config": detect_vae_config(vae, scaling_factor=0.3611, shift_factor=0.1159) if vae else None, "is_flux": True,
              "dtype": torch.float16 if stored == torch.float16 else torch.bfloat16,
              "ignored": sorted({k.split(".")[0] for k in sd if not k.startswith((prefix,) + FLUX_VAE_PREFIXES)} if prefix else set())}
@@ -272,13 +328,19 @@ def split_flux_state_dict(sd):
 
 
 def split_state_dict(sd):
-    """loader.py:449-486 without the text encoders: -> ({'unet': ..., 'vae': ...}, guess dict)."""
-    sd = preprocess_state_dict(load_torch_file(sd))
-    unet = {k[len(UNET_PREFIX):]: v for k, v in sd.items() if k.startswith(UNET_PREFIX)}
+    """loader.py:449-486 without the text encoders: -> ({'unet': ..., 'vae': ...}, guess dict).  A float8-stored checkpoint comes back with its
+    UNet as the reference's fp8 storage leaves it (quant_state.mirror_fp8_storage), every tensor a PackedTensor for dequantize_state_dict to
+    expand; bitsandbytes storage is not served for this family."""
+    from .quant_state import is_packed, mirror_fp8_storage, wrap_quantized_state_dict
+    sd = wrap_quantized_state_dict(preprocess_state_dict(load_torch_file(sd)))
+    for k, v in sd.items():
+        if is_packed(v) and not v.is_fp8:
+            raise NotImplementedError(f"{k}: bitsandbytes {v.scheme} storage is loaded for Flux transformers and T5 encoders; SD / SDXL checkpoints are not served")
+    unet = mirror_fp8_storage({k[len(UNET_PREFIX):]: v for k, v in sd.items() if k.startswith(UNET_PREFIX)}, "unet")
     vae = {k[len(VAE_PREFIX):]: v for k, v in sd.items() if k.startswith(VAE_PREFIX)}
     vae = {k: v for k, v in vae.items() if not k.startswith(("loss.", "model_ema."))}
     from .misc.diffusers_state_dict import vae_from_diffusers
-    vae = vae_from_diffusers(vae)   # loader.py:58-59
+    vae = vae_from_diffusers(_vae_as_stored(vae, VAE_PREFIX))   # loader.py:58-59
     unet_config = detect_unet_config(sd)
     is_sdxl = unet_config.get("adm_in_channels") is not None
     vae_config = detect_vae_config(vae, scaling_factor=0.13025 if is_sdxl else 0.18215, shift_factor=0.0) if vae else None
@@ -292,7 +354,7 @@ def split_state_dict(sd):
     pred_source = "marker key" if "v_pred" in sd else "default"
     probe = UNET_PREFIX + "output_blocks.11.1.transformer_blocks.0.norm1.bias"
     if pred == "epsilon" and unet_config.get("context_dim") == 1024 and unet_config.get("in_channels") == 4 and not is_sdxl and probe in sd:
-        if float(sd[probe].float().std(unbiased=False)) > 0.09:   # the population form, as huggingface_guess computes it
+        if float((sd[probe].host_float() if is_packed(sd[probe]) else sd[probe].float()).std(unbiased=False)) > 0.09:   # the population form, as huggingface_guess computes it
             pred, pred_source = "v_prediction", "SD2.x norm1.bias statistic (std > 0.09)"
     guess = {"unet_config": unet_config, "vae_config": vae_config, "is_sdxl": is_sdxl, "prediction_type": pred, "prediction_type_source": pred_source,
              "ztsnr": "ztsnr" in sd, "ignored": sorted({k.split(".")[0] for k in sd if not k.startswith((UNET_PREFIX, VAE_PREFIX))})}
@@ -306,19 +368,31 @@ def forge_loader(sd, loras=None, device="cuda", prediction_type=None, additional
     additional_state_dicts: further files / dicts (VAE, CLIP-L, T5) merged into the checkpoint by replace_state_dict, as the reference's keyword
     (loader.py:449-452, :498): a Flux GGUF holds the transformer only.  dtype: compute type of a Flux transformer, overriding the stored one.
     `.gguf` inputs are dequantised on the device (dequantize_state_dict); the text encoders' state dicts are left on the engine as
-    `engine.text_encoder_state_dicts` ({'t5xxl': ..., 'clip_l': ...}, keys as IntegratedT5 / IntegratedCLIP take them)."""
+    `engine.text_encoder_state_dicts` ({'t5xxl': ..., 'clip_l': ...}, keys as IntegratedT5 / IntegratedCLIP take them).
+    float8 and bitsandbytes nf4 / fp4 storage (flux1-dev-fp8, t5xxl_fp8_e4m3fn, flux1-dev-bnb-nf4) takes the same device route: the tensors are
+    wrapped (quant_state.wrap_quantized_state_dict), each component is brought to what the reference's storage type makes of it
+    (quant_state.mirror_fp8_storage: per component, wider tensors of an fp8-majority component are rounded to fp8) and expanded once into 16-bit
+    weights.  Served: Flux transformers (fp8, nf4, fp4), T5 (fp8, nf4, fp4) and CLIP-L (fp8) side files, SD / SDXL UNets (fp8)."""
     from .patcher.lora import merge_loras_into_state_dict
+    from .quant_state import is_packed, mirror_fp8_storage, wrap_quantized_state_dict
     sd = load_torch_file(sd)
     if additional_state_dicts:
         sd = dict(sd)
         for asd in additional_state_dicts:
             replace_state_dict(sd, load_torch_file(asd))
+    sd = wrap_quantized_state_dict(sd)
     if flux_prefix(sd) is not None:
         from .diffusion_engine.base import build_flux_engine
         from .patcher.lora import merge_loras_into_flux_state_dict
         parts, guess = split_flux_state_dict(sd)
         if dtype is not None:
             guess["dtype"] = dtype
+        for k, v in parts["text_encoders"].get("clip_l", {}).items():
+            if is_packed(v) and not v.is_fp8:
+                raise NotImplementedError(f"{CLIP_L_PREFIX}{k[len('transformer.'):]}: bitsandbytes {v.scheme} storage is not served for CLIP-L")
+        parts["transformer"] = mirror_fp8_storage(parts["transformer"], "flux")
+        if "t5xxl" in parts["text_encoders"]:      # CLIP-L is built in its own type whatever the file's: its fp8 tensors are only expanded
+            parts["text_encoders"]["t5xxl"] = mirror_fp8_storage(parts["text_encoders"]["t5xxl"], "t5")
         parts["transformer"] = dequantize_state_dict(parts["transformer"], device, guess["dtype"])
         parts["vae"] = dequantize_state_dict(parts["vae"], device, torch.float16)
         tsd, report = parts["transformer"], None
@@ -336,7 +410,7 @@ def forge_loader(sd, loras=None, device="cuda", prediction_type=None, additional
     parts, guess = split_state_dict(sd)
     if prediction_type is not None:
         guess["prediction_type"] = prediction_type
-    unet_sd = parts["unet"]
+    unet_sd = dequantize_state_dict(parts["unet"], device, torch.float16)      # fp8 storage: expanded to the UNet's compute type (every code fits)
     report = None
     if loras:
         unet_sd, report = merge_loras_into_state_dict(unet_sd, guess["unet_config"], [(load_torch_file(l), s) for l, s in loras], device=device)

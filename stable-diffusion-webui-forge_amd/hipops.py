@@ -701,6 +701,83 @@ def gguf_dequant(raw, qtype, shape, dtype=torch.bfloat16, out=None):
     return out
 
 
+FP8_KINDS = {"fp8_e4m3fn": 0, "fp8_e5m2": 1, torch.float8_e4m3fn: 0, torch.float8_e5m2: 1}
+
+
+def _packed_source(what, raw, dtype):
+    if not isinstance(raw, torch.Tensor) or not raw.is_cuda or raw.dtype != torch.uint8 or not raw.is_contiguous():
+        raise TypeError("%s expects a contiguous uint8 device tensor, got %s on %s" % (what, getattr(raw, "dtype", type(raw)), getattr(raw, "device", "the host")))
+    sfx = {torch.float16: "_f16", torch.bfloat16: "_bf16"}.get(dtype)
+    if sfx is None:
+        raise TypeError("%s produces fp16 or bf16, not %s" % (what, dtype))
+    return sfx
+
+
+def _expanded_out(what, out, shape, n, dtype, device):
+    """the output of an expansion: a fresh tensor, or the caller's -- which the kernel writes n 16-bit elements into, so it must be exactly that"""
+    if out is None:
+        return empty(shape, dtype, device)
+    if not out.is_cuda or out.device != device or out.dtype != dtype or out.numel() != n or not out.is_contiguous():
+        raise ValueError("%s: out must be a contiguous %s tensor of %d elements on %s, got %s x %d on %s"
+                         % (what, dtype, n, device, out.dtype, out.numel(), out.device))
+    return out
+
+
+def _numel(shape):
+    n = 1
+    for s in shape:
+        n *= s
+    return n
+
+
+def fp8_expand(raw, kind, shape, dtype=torch.bfloat16, out=None):
+    """float8 codes (`raw`: a contiguous uint8 device tensor; `kind`: 0 / 'fp8_e4m3fn' / torch.float8_e4m3fn, 1 / 'fp8_e5m2' / torch.float8_e5m2)
+    -> a `shape`-shaped fp16 / bf16 device tensor holding exactly the values of the codes (include/fmx.h, float8 section)."""
+    sfx = _packed_source("fp8_expand", raw, dtype)
+    shape = tuple(int(s) for s in shape)
+    n = _numel(shape)
+    if raw.numel() != n:
+        raise ValueError("fp8_expand: %d bytes do not hold %s float8 weights" % (raw.numel(), shape))
+    out = _expanded_out("fp8_expand", out, shape, n, dtype, raw.device)
+    _lib.check(getattr(_lib.lib(), "fmx_fp8_expand" + sfx)(int(FP8_KINDS.get(kind, kind)), _p(raw), _p(out), n, stream_ptr()), "fmx_fp8_expand" + sfx)
+    return out
+
+
+def bnb4_dequant(packed, quant_state, dtype=torch.bfloat16, out=None):
+    """bitsandbytes 4-bit weights (`packed`: a contiguous uint8 device tensor of (n + 1) / 2 bytes; `quant_state`: a backend.quant_state.BnbQuantState
+    whose tensors are on the same device) -> a fp16 / bf16 device tensor of quant_state.shape: code[nibble] * block scale in fp32, rounded once
+    (include/fmx.h, bitsandbytes section).  One launch; the nested scales are computed inside it."""
+    sfx = _packed_source("bnb4_dequant", packed, dtype)
+    qs = quant_state
+    shape = tuple(int(s) for s in qs.shape)
+    n = _numel(shape)
+    if packed.numel() != (n + 1) // 2:
+        raise ValueError("bnb4_dequant: %d bytes do not hold %s 4-bit weights" % (packed.numel(), shape))
+    bs = int(qs.blocksize)
+    if bs < 64 or bs > 4096 or bs & (bs - 1):
+        raise ValueError("bnb4_dequant: blocksize %d must be a power of two from 64 to 4096" % bs)
+    nblocks = (n + bs - 1) // bs
+
+    def side(t, what, want_dtype, numel):
+        if not t.is_cuda or t.device != packed.device or t.dtype != want_dtype or not t.is_contiguous() or t.numel() != numel:
+            raise ValueError("bnb4_dequant: %s must be a contiguous %s tensor of %d values on %s, got %s x %d on %s"
+                             % (what, want_dtype, numel, packed.device, t.dtype, t.numel(), t.device))
+        return t
+
+    code = side(qs.code, "code", torch.float32, 16)
+    if qs.nested:
+        bs2 = int(qs.blocksize2)
+        if bs2 < 64 or bs2 & (bs2 - 1):
+            raise ValueError("bnb4_dequant: nested blocksize %d must be a power of two of at least 64" % bs2)
+        args = (None, _p(side(qs.absmax, "absmax", torch.uint8, nblocks)), _p(side(qs.code2, "nested code", torch.float32, 256)),
+                _p(side(qs.absmax2, "nested absmax", torch.float32, (nblocks + bs2 - 1) // bs2)), float(qs.offset), bs2)
+    else:
+        args = (_p(side(qs.absmax, "absmax", torch.float32, nblocks)), None, None, None, 0.0, 0)
+    out = _expanded_out("bnb4_dequant", out, shape, n, dtype, packed.device)
+    _lib.check(getattr(_lib.lib(), "fmx_bnb4_dequant" + sfx)(_p(packed), _p(code), *args, bs, _p(out), n, stream_ptr()), "fmx_bnb4_dequant" + sfx)
+    return out
+
+
 def unet_pack_input(x, sigma, reps, sigma_data=1.0, out=None):
     b, c, h, w = x.shape
     if out is None:
