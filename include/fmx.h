@@ -52,6 +52,8 @@
  *   fmx_bnb4_dequant_*     backend/memory_management.py:311-337 (state_dict_dtype), backend/operations_bnb.py (ForgeParams4bit, functional_linear_4bits),
  *                          backend/operations.py:353-389 (the manual cast of fp8-stored weights)
  *   fmx_freeu_*            FreeU v2 extensions-builtin/sd_forge_freeu/scripts/forge_freeu.py:9-58 (Fourier_filter, output_block_patch)
+ *   fmx_row_abs_quantile_f32 / fmx_dynthresh_f32
+ *                          Dynamic Thresholding (CFG-Fix) extensions-builtin/sd_forge_dynamic_thresholding/lib_dynamic_thresholding/dynthres_core.py:61-125
  */
 #ifndef FMX_H
 #define FMX_H
@@ -621,6 +623,51 @@ int fmx_freeu_reduce_f16(const void* h, int32_t c_h, const void* skip, int32_t c
                          int32_t nchunks, float* workspace, int64_t workspace_floats, void* stream);
 int fmx_freeu_apply_f16(void* h, int32_t c_h, void* skip, int32_t c_s, int32_t n, int32_t hh, int32_t ww, const float* trig, int32_t nchunks,
                         float* workspace, int64_t workspace_floats, float b, float s, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Dynamic Thresholding (CFG-Fix): extensions-builtin/sd_forge_dynamic_thresholding/lib_dynamic_thresholding/dynthres_core.py:61-125.
+ * New symbols only: no existing signature moves, the ABI number stays 12.  fp32 in and out, rows of contiguous values (NCHW planes).
+ *
+ * fmx_row_abs_quantile_f32: x [rows][n], center [rows], out [rows / rows_per_group].  For every group of rows_per_group consecutive rows,
+ *   out[g] = the q-quantile (linear interpolation, as torch.quantile) of the N = rows_per_group * n values |x[r][i] - center[r]| of the group:
+ *   pos = (float)q * (float)(N - 1) in fp32, lo = floor(pos), hi = ceil(pos), w = pos - lo, v = the values in ascending order,
+ *   out = w < 0.5 ? fma(w, v[hi] - v[lo], v[lo]) : fma(w - 1, v[hi] - v[lo], v[hi])      (torch.lerp as the CPU evaluates it)
+ *   -- bit for bit what torch.quantile returns on the CPU for finite inputs.  The two order statistics are SELECTED, not sorted: non-negative
+ *   floats order like their bit patterns, so three most-significant-digit passes (11 + 11 + 9 bits) over the values, each a histogram in LDS
+ *   built with integer atomics (whose result does not depend on their order), fix v[lo] and how many values equal it; v[hi] is v[lo] again
+ *   when enough values tie with it, else the smallest value above it (one more pass).  q == 1 takes one max pass (the same bits: w is 0).
+ *   One workgroup per group; the values are re-read from memory (L2) in every pass, no copy of the data is made.
+ *   Requirements (FMX_E_BADARG otherwise, before any launch): pointers non-null; rows, n, rows_per_group > 0; rows % rows_per_group == 0;
+ *   rows_per_group * n <= 2^31 - 1; 0 <= q <= 1.
+ *
+ * fmx_dynthresh_f32: cond, uncond, out [b][c][hw] (the two denoised predictions; out may alias neither).  With rel = cond - uncond:
+ *   mim = uncond + rel * mimic,  cfg_t = uncond + rel * cfg;  per (sample, channel) row: means (per-chunk partial sums of
+ *   FMX_DYNTHRESH_CHUNK consecutive values, added in chunk order, over hw) and centred values target - mean.
+ *   scale references, per row (FMX_DYNTHRESH_SEPARATE) or one for the whole tensor, batch included (the means stay per row):
+ *     AD : mim_ref = max |mim_centred|, cfg_ref = the `percentile`-quantile of |cfg_centred| (the selection above)
+ *     STD: the unbiased standard deviation of each (FMX_DYNTHRESH_STD; two passes: the mean of the centred values, then the squares)
+ *   result:  FMX_DYNTHRESH_ZERO:  cfg_t * (mim_ref / cfg_ref)
+ *            else with STD:       cfg_centred / cfg_ref * mim_ref + cfg_mean
+ *            else (AD):           m = max(mim_ref, cfg_ref);  clamp(cfg_centred, -m, m) / m * mim_ref + cfg_mean
+ *   and, when phi != 1:  result * (float)phi + cfg_t * (float)(1 - phi).
+ *   Every element-wise expression is evaluated in the reference's order with one rounding per operation (no contraction); sums are block
+ *   reductions of a fixed shape -- the same bits on every run.  A degenerate row is not special-cased: a constant row gives 0 / 0 = NaN,
+ *   STD with one value per row gives NaN, as the reference does.  Three launches: partial sums, references (one workgroup per row or one
+ *   for the tensor), apply.
+ *   workspace : fp32, at least FMX_DYNTHRESH_WORKSPACE_FLOATS(b * c, hw) values, 16-byte aligned.
+ *   Requirements (FMX_E_BADARG otherwise, before any launch): pointers non-null, out distinct from cond and uncond; b, c, hw > 0;
+ *   b * c <= 65535; b * c * hw <= 2^31 - 1; 0 <= percentile <= 1; no unknown flag bits.
+ * ---------------------------------------------------------------------------------------------- */
+#define FMX_DYNTHRESH_SEPARATE 1 /* "Separate feature channels": scale references per row */
+#define FMX_DYNTHRESH_ZERO 2     /* scaling startpoint ZERO (else MEAN) */
+#define FMX_DYNTHRESH_STD 4      /* variability measure STD (else AD) */
+#define FMX_DYNTHRESH_CHUNK 2048
+#define FMX_DYNTHRESH_NCHUNKS(hw) (((int64_t)(hw) + FMX_DYNTHRESH_CHUNK - 1) / FMX_DYNTHRESH_CHUNK)
+/* partial sums [rows][nchunks][2] | means [rows][2] | references [rows][2] (mimic, cfg) */
+#define FMX_DYNTHRESH_WORKSPACE_FLOATS(rows, hw) ((int64_t)(rows) * FMX_DYNTHRESH_NCHUNKS(hw) * 2 + (int64_t)(rows) * 4)
+int fmx_row_abs_quantile_f32(const float* x, const float* center, int32_t rows, int32_t n, int32_t rows_per_group, float q, float* out, void* stream);
+int fmx_dynthresh_f32(const float* cond, const float* uncond, int32_t b, int32_t c, int32_t hw, float mimic, float cfg, float percentile,
+                      int32_t flags, double phi, float* workspace, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * HIP-graph helpers: capture everything launched on `stream` between begin/end into an executable graph.

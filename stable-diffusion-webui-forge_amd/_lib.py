@@ -175,6 +175,10 @@ for _n in ("fmx_bnb4_dequant_f16", "fmx_bnb4_dequant_bf16"):   # (packed, code16
 # native FreeU (h, c_h, skip, c_s, n, hh, ww, trig, nchunks, workspace, workspace_floats [, b, s], stream): new symbols, the ABI number does not move
 SIGNATURES["fmx_freeu_reduce_f16"] = [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _vp]
 SIGNATURES["fmx_freeu_apply_f16"] = [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _f32, _f32, _vp]
+# native Dynamic Thresholding: (x, center, rows, n, rows_per_group, q, out, stream) and (cond, uncond, b, c, hw, mimic, cfg, percentile, flags,
+# phi, workspace, out, stream): new symbols, the ABI number does not move
+SIGNATURES["fmx_row_abs_quantile_f32"] = [_vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp]
+SIGNATURES["fmx_dynthresh_f32"] = [_vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _i32, C.c_double, _vp, _vp, _vp]
 
 
 def source_tree_hash():

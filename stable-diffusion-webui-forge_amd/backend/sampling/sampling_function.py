@@ -223,7 +223,8 @@ def calc_cond_uncond_batch(model, cond, uncond, x_in, timestep, model_options, c
 
 def sampling_function_inner(model, x, timestep, uncond, cond, cond_scale, model_options={}, seed=None, return_full=False):
     """:292-322, including the sampler_pre_cfg / sampler_cfg / sampler_post_cfg function hooks and the edit-strength form of the CFG
-    formula for AND-composed prompts."""
+    formula for AND-composed prompts.  model_options["dynthresh"] (without a Python sampler_cfg_function) is the native form of the Dynamic
+    Thresholding script's CFG function: it does not move the step off the fused route."""
     from ... import hipops as ops
     edit_strength = sum((item["strength"] if "strength" in item else 1) for item in cond)
     if math.isclose(cond_scale, 1.0) and not model_options.get("disable_cfg1_optimization", False):
@@ -239,6 +240,17 @@ def sampling_function_inner(model, x, timestep, uncond, cond, cond_scale, model_
         args = {"cond": x - cond_pred, "uncond": x - uncond_pred, "cond_scale": cond_scale, "timestep": timestep, "input": x, "sigma": timestep,
                 "cond_denoised": cond_pred, "uncond_denoised": uncond_pred, "model": model, "model_options": model_options}
         cfg_result = x - model_options["sampler_cfg_function"](args)
+    elif model_options.get("dynthresh") is not None:
+        # native Dynamic Thresholding (backend/patcher/dynthresh.py): the schedule on the host, one op on the two denoised predictions of
+        # whichever route produced them; the fused route's own CFG combination is discarded
+        from ..modules.k_model import host_sigmas
+        from ..patcher.dynthresh import scales_for_sigma
+        dyn = model_options["dynthresh"]
+        mimic, cfg = scales_for_sigma(dyn, model.predictor, host_sigmas(timestep), cond_scale)
+        if uncond_pred is None:     # Flux at cfg scale 1: no uncond call; the reference's function sees zeros there
+            uncond_pred = torch.zeros_like(cond_pred)
+        cfg_result = ops.dynthresh(cond_pred.contiguous(), uncond_pred.contiguous(), mimic, cfg, dyn.threshold_percentile,
+                                   dyn.separate_feature_channels == "enable", dyn.scaling_startpoint, dyn.variability_measure, dyn.interpolate_phi)
     elif cfg_result is None:
         k = cond_scale * edit_strength if not math.isclose(edit_strength, 1.0) else cond_scale
         cfg_result = ops.lincomb([uncond_pred.contiguous(), cond_pred.contiguous()], [1.0 - k, k])  # uncond + (cond - uncond) * k

@@ -645,6 +645,55 @@ def freeu(h, skip, b, s):
     return h, skip
 
 
+DYNTHRESH_SEPARATE, DYNTHRESH_ZERO, DYNTHRESH_STD = 1, 2, 4   # FMX_DYNTHRESH_* of include/fmx.h
+DYNTHRESH_CHUNK = 2048
+
+
+def _check_f32_rows(what, *ts):
+    for t in ts:
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+            raise TypeError(f"{what} expects contiguous fp32 device tensors")
+
+
+def row_abs_quantile(x, center, q, rows_per_group=1):
+    """x fp32 [rows, n], center fp32 [rows] -> fp32 [rows / rows_per_group]: per group of consecutive rows, torch.quantile(|x - center|, q)
+    over the group's values, bit for bit (include/fmx.h, section "Dynamic Thresholding"): an order-statistic selection, no sort."""
+    _check_f32_rows("row_abs_quantile", x, center)
+    if x.dim() != 2 or center.shape != (x.shape[0],):
+        raise ValueError(f"row_abs_quantile expects x [rows, n] and center [rows], got {tuple(x.shape)} and {tuple(center.shape)}")
+    rows, n = x.shape
+    if rows_per_group <= 0 or rows % rows_per_group:
+        raise ValueError(f"row_abs_quantile: {rows} rows are not whole groups of {rows_per_group}")
+    out = torch.empty(rows // rows_per_group, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().fmx_row_abs_quantile_f32(_p(x), _p(center), rows, n, rows_per_group, float(q), _p(out), stream_ptr()),
+               "fmx_row_abs_quantile_f32")
+    return out
+
+
+def dynthresh(cond, uncond, mimic, cfg, percentile, separate, startpoint, variability, phi, out=None):
+    """Dynamic Thresholding of the two denoised predictions [B, C, H, W] fp32 (include/fmx.h, section "Dynamic Thresholding"): `mimic` / `cfg` are
+    the step's interpreted scales, `separate` a bool, `startpoint` "MEAN" | "ZERO", `variability` "AD" | "STD".  -> out (a new tensor unless given;
+    it may alias neither input)."""
+    _check_f32_rows("dynthresh", cond, uncond)
+    if cond.dim() != 4 or cond.shape != uncond.shape or cond.device != uncond.device:
+        raise ValueError(f"dynthresh expects two [B, C, H, W] tensors of one shape, got {tuple(cond.shape)} and {tuple(uncond.shape)}")
+    if startpoint not in ("MEAN", "ZERO") or variability not in ("AD", "STD"):
+        raise ValueError(f"dynthresh: unknown startpoint / variability {startpoint!r} / {variability!r}")
+    b, c, hh, ww = cond.shape
+    hw = hh * ww
+    if out is None:
+        out = torch.empty_like(cond)
+    else:
+        _check_f32_rows("dynthresh", out)
+        if out.shape != cond.shape:
+            raise ValueError("dynthresh: out must have the inputs' shape")
+    flags = (DYNTHRESH_SEPARATE if separate else 0) | (DYNTHRESH_ZERO if startpoint == "ZERO" else 0) | (DYNTHRESH_STD if variability == "STD" else 0)
+    ws = torch.empty(b * c * (-(-hw // DYNTHRESH_CHUNK)) * 2 + b * c * 4, dtype=torch.float32, device=cond.device)   # FMX_DYNTHRESH_WORKSPACE_FLOATS
+    _lib.check(_lib.lib().fmx_dynthresh_f32(_p(cond), _p(uncond), b, c, hw, float(mimic), float(cfg), float(percentile), flags, float(phi), _p(ws),
+                                            _p(out), stream_ptr()), "fmx_dynthresh_f32")
+    return out
+
+
 ACT_QUICK_GELU, ACT_GELU_ERF, ACT_RELU = 0, 1, 2
 
 

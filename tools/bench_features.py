@@ -5,6 +5,8 @@ bench (bench.py): this is the check that the §8f rows hold up at the BASELINE s
 batch sizes -- and what they cost.
 
     python tools/bench_features.py [--steps 6] [--only samplers,controlnet,hooks,freeu,and,hires]
+    python tools/bench_features.py --only dynthresh  Dynamic Thresholding: plain / native at percentile 1.0 and 0.99 / the same arithmetic as a Python
+                                                     sampler_cfg_function, interleaved in one process, device events around every job
     python tools/bench_features.py --only taesd      the TAESD decode of batch x (res/8)^2 SDXL-shaped latents (synthetic weights, fp16) next to the Full
                                                      VAE decode of the same latents in the same process: median of 5 after warm-up, events around the calls
 """
@@ -179,8 +181,78 @@ def main():
                           "freeu_calls_per_unet_call": [list(s) for s in per_call], "freeu_kernels_ms_per_unet_call": round(sorted(kern)[len(kern) // 2], 3),
                           "finite": finite, "shape": list(lat.shape)}), flush=True)
 
+    def dynthresh_leg(rounds=5):
+        """Plain, native Dynamic Thresholding (model option, the step stays on the fused route) at threshold percentile 1.0 and 0.99, and the
+        same arithmetic as a Python sampler_cfg_function installed through set_model_sampler_cfg_function (tests/dynthresh_refs.py in torch
+        fp32: the stacked general route, torch.quantile, a device read of the timestep per step) -- primed once each, then timed alternately,
+        `rounds` jobs of a.steps steps per variant in this one process (each after an untimed two-step job on the same route), device events around each job.  Also the op on its own on the job's
+        latent shape (events, median of 20): what the native route adds to a step."""
+        import dynthresh_refs as dr
+        from forge_amd import hipops as ops
+        from forge_amd.backend.patcher import dynthresh as pd
+
+        def native(pct):
+            return pd.patch_dynthresh(eng.forge_objects.unet, 7.0, pct)
+
+        def hooked(pct):
+            u = eng.forge_objects.unet.clone()
+            u.set_model_sampler_cfg_function(dr.sampler_cfg_function_for(pd.DynThreshParams(True, 7.0, pct), u.model.predictor))
+            return u
+        variants = {"plain": None, "native_p1.0": native(1.0), "native_p0.99": native(0.99), "hooked_p1.0": hooked(1.0), "hooked_p0.99": hooked(0.99)}
+        saved = eng.forge_objects_after_applying_lora
+
+        def once(unet, n):
+            if unet is not None:
+                eng.forge_objects_after_applying_lora = saved.shallow_copy()
+                eng.forge_objects_after_applying_lora.unet = unet
+            try:
+                pr = processing.StableDiffusionProcessingTxt2Img(sd_model=eng, c=c1, uc=u1, seed=1, sampler_name="Euler", batch_size=b, steps=n,
+                                                                 cfg_scale=7.0, width=width, height=height, do_decode=False)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                lat = processing.process_images(pr).latents
+                e1.record()
+                torch.cuda.synchronize()
+                return e0.elapsed_time(e1), lat
+            finally:
+                eng.forge_objects_after_applying_lora = saved
+                eng.forge_objects = saved.shallow_copy()
+        for unet in variants.values():    # priming (arena, caches, graphs)
+            once(unet, 4)
+        ms = {k: [] for k in variants}
+        finite = True
+        for _ in range(rounds):
+            for k, unet in variants.items():
+                once(unet, 2)             # a job on another route came before: what follows a change of route (caches keyed on it) is not timed
+                dt, lat = once(unet, a.steps)
+                ms[k].append(round(dt / a.steps, 2))
+                finite = finite and bool(torch.isfinite(lat).all())
+        med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+        x, y = torch.randn(lat.shape, device=dev), torch.randn(lat.shape, device=dev)
+        op_ms = {}
+        for name, args in (("separate_p1.0", (1.0, True, "MEAN", "AD")), ("separate_p0.99", (0.99, True, "MEAN", "AD")), ("separate_std", (1.0, True, "MEAN", "STD")),
+                           ("whole_tensor_p0.99", (0.99, False, "MEAN", "AD"))):
+            t = []
+            for i in range(23):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                ops.dynthresh(x, y, 7.0, 12.0, *args, 1.0)
+                e1.record()
+                torch.cuda.synchronize()
+                if i >= 3:
+                    t.append(e0.elapsed_time(e1))
+            op_ms[name] = round(sorted(t)[len(t) // 2], 4)
+        print(json.dumps({"case": "Dynamic Thresholding (mimic 7, CFG 7): plain vs native (model option, fused route) vs hooked (Python sampler_cfg_function, "
+                                  "general route)", "sampler": "Euler", "steps": a.steps, "rounds": rounds, "ms_per_step": med, "ms_per_step_rounds": ms,
+                          "native_minus_plain_ms": {k: round(med[k] - med["plain"], 2) for k in med if k.startswith("native")},
+                          "hooked_minus_native_ms": {p_: round(med["hooked_" + p_] - med["native_" + p_], 2) for p_ in ("p1.0", "p0.99")},
+                          "dynthresh_op_ms": op_ms, "finite": finite, "shape": list(lat.shape)}), flush=True)
+
     if "one" in what:
         run(f"{width}x{height}", sampler="Euler")
+    if "dynthresh" in what:
+        dynthresh_leg()
     if "freeu" in what:
         freeu_leg()
     if "samplers" in what:
