@@ -1,5 +1,5 @@
 """fp64 references and ulp tolerances shared by the kernel-level parity tests (tests/test_gpu_kernels_bf16.py, tests/test_gpu_small_kernels.py,
-tests/test_gpu_gemm_windows.py, tests/test_gpu_vae_direct.py) and their CPU companion (tests/test_kernel_ref_teeth.py), which plants one plausible bug into each reference and checks that the GPU tests'
+tests/test_gpu_gemm_windows.py, tests/test_gpu_vae_direct.py, tests/test_gpu_sampler_kernels.py) and their CPU companion (tests/test_kernel_ref_teeth.py), which plants one plausible bug into each reference and checks that the GPU tests'
 tolerance would reject it.
 
 Discipline: every reference is the same operation in fp64 on the kernel's own rounded inputs (the fp16 / bf16 tensors it read, upcast).
@@ -8,6 +8,7 @@ A tolerance is `ulps` units in the last place of the REFERENCE value in the outp
 conftest.py): the test files import it by name."""
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -545,3 +546,289 @@ def attn64_emul(q, k, v, nk, scale, dtype, step=64, split=False, plant=None):
     else:
         _, l, o = _attn64_range(qs, k, v, nk, 0, -(-nk // step) * step, step, dtype, plant, False)
     return (o * (1.0 / l)[..., None]).to(dtype)
+
+
+# ---- the sampler-step kernels (tests/test_gpu_sampler_kernels.py) ---------------------------------------------------------------------------------
+# fmx_unet_pack_input, fmx_im2col3x3_smallc, fmx_cfg_combine, fmx_sampler_euler_step / _lincomb3 / _lincomb / _error_norm, fmx_philox_randn
+# (csrc/fmx_elementwise.hip).  Scalars that the wrappers hand over as C `float` (coefficients, sigma, sigma_next, noise_scale, cond_scale, sigma_data,
+# atol, rtol) are part of the operation: every reference below takes them through f32() first, as timestep_ref rounds its argument.
+#
+# fp32 outputs: per-element absolute bound  R * 2^-24 * sum|terms|  (assert_within_bound), sum|terms| = the magnitudes of the terms the fp64 reference
+# adds for that element, R = the number of fp32 roundings that the value of one such term passes through on its way to the stored result, counted on
+# the longest chain of the kernel's source INCLUDING the roundings of the side inputs that are formed in the kernel and multiply into the term (a
+# rounding of relative size 2^-24 of a factor is one of the term).  Every rounding is at most 2^-24 of a partial result that is no larger than the
+# summed magnitudes, fp32 `/` and sqrtf are correctly rounded in this build (csrc/Makefile: -O3, no fast-math), and FMA contraction only removes
+# roundings.  None of the counts below comes from a GPU run.
+U32 = 2.0 ** -24
+#   fmx_sampler_lincomb, N terms, accumulated left to right:  coef0 * src0 (1), then per further term one product and one add.  The first term passes
+#     through its product and N - 1 adds: R = N (n_terms).
+#   fmx_sampler_lincomb3:  bc * d0 (1), + cc * d1 (2), a * x + that (3): R = 3 (2 without old_denoised; the test uses 3 throughout).
+LINCOMB3_R = 3
+#   fmx_sampler_euler_step:  the term d * dt passes through  x - den (1), / sigma (2), * dt (3) where dt = sigma_next - sigma is itself rounded in
+#     the kernel (4), x + that (5), + noise * noise_scale (6): R = 6.  terms: |x|, |(x - den) / sigma * dt|, |noise * noise_scale|.
+EULER_R = 6
+#   fmx_cfg_combine, v_prediction / edm with two halves (the longest formula of the kernel):  the term B * out passes through  s * s (1) and
+#     sigma_data * sigma_data (2), their sum v (3), sqrtf(v) (4), s * sigma_data (5), the quotient cb (6), out * cb (7), x * ca + that (8): 8 roundings
+#     up to the stored cond_pred / uncond_pred, then dc - du (9), * cond_scale (10), du + that (11).  The term A * x passes through fewer (s * s, sigma_data^2,
+#     v, the quotient ca, x * ca, the sum: 6 and the same last 3), epsilon prediction through 2 and 5 (out * s, x - that; the same last 3).  One R per kernel:
+#     denoised R = 11, cond_pred / uncond_pred R = 8.  terms of denoised (reps == 2): |A x| + |B eu|, |A x| + |B ec|, |cond_scale (dc - du)|; with one
+#     half: |A x| + |B ec| and |cond_scale dc|.
+#     What the count does NOT model: a rounding made in du (dc) before the subtraction reaches denoised multiplied by 1 - cond_scale (cond_scale).  At
+#     cond_scale 7 and a small sigma (x dominates, dc ~ du ~ x, the guidance term is small) the un-fused worst case is (2 per half) * (6 + 7) + the
+#     shared ca / cb roundings and the final add ~ 30 * 2^-24 |A x| against the bound's 22 * 2^-24 |A x|: reachable only if every rounding of both
+#     halves is a full half-ulp of the adverse sign at the top of x's binade.  The figures below are the measure of how far real data stays from that.
+CFG_R, CFG_PRED_R = 11, 8
+#   fmx_unet_pack_input: fp16 output, a few fp32 operations (s * s + sd^2, rsqrtf, one product) and one rounding: ELEM_TOL[float16] as it stands.
+#   fmx_im2col3x3_smallc: a 16-bit word shuffle: bit equality.
+#   fmx_sampler_error_norm: a sum of non-negative fp32 terms, so the bound is relative.  Per element  rtol * max (1) in delta, lo - hi (2), / delta (3):
+#     r carries 3, r * r twice that and its own rounding = 7.  Summation depth from the source: per-thread strided sums of ceil(n / 65536) terms (256
+#     blocks x 256 threads), 6 shuffle levels, 4 waves, 256 partials added in sequence.  (7 + depth) * 2^-24 on the sum of squares, half of it on the
+#     root: error_norm_rel_bound(n).  (Not in the formula, which is kept as stated: the four roundings behind the sum -- 1 / n, its root, the root of the
+#     sum, their product -- which are not halved; three of the counted adds are 0 + x and exact, so the worst case is 2.5 * 2^-24 above the formula, 2% of
+#     it at the smallest n.)
+ERRNORM_TERM_R = 7
+#   fmx_philox_randn: the four raw words bit-exact against oracle/rng.py; the normals within atol 2e-6 (the device logf / sinf), as
+#     tests/test_gpu_kernels.py::test_philox_bit_exact has it.  The GPU file prints the figure per case; it is not tightened.
+PHILOX_ATOL = 2e-6
+#
+# Worst excess (units of the bound / tolerance) over every case of tests/test_gpu_sampler_kernels.py: the emulations below (the kernels' formulas in
+# plain fp32 torch, no FMA; tests/test_kernel_ref_teeth.py asserts <= 1 and prints them) and the `MEASURED` lines of the GPU file on MI355X:
+#   kernel                 emulation    MI355X
+#   unet_pack_input        0.500        0.500
+#   im2col3x3_smallc       bit-equal    bit-equal
+#   cfg_combine denoised   0.541        0.541
+#   cfg_combine preds      0.274        0.274
+#   euler_step             0.399        0.399
+#   lincomb3               0.791        0.705
+#   lincomb                0.968        0.968
+#   error_norm             0.042        0.042
+#   philox_randn normals   (host libm)  0.679 (1.36e-6 absolute, n = 16384)
+# (lincomb's 0.968 is the single product of a one-term case, n = 4099, where the bound is that one rounding: nothing to give.  Several MI355X figures
+# equal the emulation's to three digits although the kernels' code does contract (v_fma / v_fmac in the ISA): fusing a product into an add changes the
+# final fp32 value of few elements, and not of the worst ones here, whose error comes from the earlier roundings and the last one.)
+
+
+def f32(v):
+    """a host scalar as the C `float` argument the kernel receives"""
+    return float(np.float32(v))
+
+
+def _taps(xc, transposed=False):
+    """xc [b, c, h, w] -> [b, h, w, 9, c]: the nine zero-padded 3x3 neighbours of every pixel, tap = ky * 3 + kx (transposed: kx * 3 + ky, a planted bug)"""
+    b, c, h, w = xc.shape
+    xp = F.pad(xc, (1, 1, 1, 1))
+    taps = [xp[:, :, ky:ky + h, kx:kx + w] for ky in range(3) for kx in range(3)]
+    if transposed:
+        taps = [taps[kx * 3 + ky] for ky in range(3) for kx in range(3)]
+    return torch.stack(taps, 1).permute(0, 3, 4, 1, 2)
+
+
+def _pack_rows(t, reps, ch_major=False):
+    """[b, h, w, 9, c] -> [reps * b * h * w, 64]: column tap * c + ch (ch_major: ch * 9 + tap, a planted bug), zeros from 9 c on, `reps` stacked copies"""
+    b, h, w, _, c = t.shape
+    if ch_major:
+        t = t.transpose(3, 4)
+    out = torch.zeros(b * h * w, 64, dtype=t.dtype)
+    out[:, :9 * c] = t.reshape(b * h * w, 9 * c)
+    return out.repeat(reps, 1)
+
+
+def pack_input_ref(x, sigma, sigma_data, reps):
+    """fmx_unet_pack_input: x fp32 [b, c, h, w], sigma fp32 [b] -> fp64 [reps * b * h * w, 64] of x / sqrt(sigma^2 + sigma_data^2)"""
+    b = x.shape[0]
+    xc = x.double() / torch.sqrt(sigma.double() ** 2 + f32(sigma_data) ** 2).view(b, 1, 1, 1)
+    return _pack_rows(_taps(xc), reps)
+
+
+def pack_input_emul(x, sigma, sigma_data, reps, plant=None):
+    """the kernel's arithmetic in fp32 torch (1 / sqrt for rsqrtf), rounded once to fp16.  plant: None, "ch_major" (column ch * 9 + tap), "kykx" (taps
+    transposed), "sigma_of_image0", "sd2_dropped" (x / sqrt(sigma^2): the term gone), "sd_not_squared" (sigma^2 + sigma_data: invisible at sigma_data 1)"""
+    b = x.shape[0]
+    s = sigma.float()
+    if plant == "sigma_of_image0":
+        s = s[:1].expand(b)
+    sd = torch.tensor(f32(sigma_data), dtype=torch.float32)
+    sd2 = {"sd2_dropped": torch.zeros(()), "sd_not_squared": sd}.get(plant, sd * sd)
+    xc = x.float() * (1.0 / torch.sqrt(s * s + sd2)).view(b, 1, 1, 1)
+    return _pack_rows(_taps(xc, transposed=plant == "kykx"), reps, ch_major=plant == "ch_major").half()
+
+
+def im2col_smallc_ref(x, c):
+    """fmx_im2col3x3_smallc: x 16-bit [n, h, w, ldx] -> the same type [n * h * w, 64], moved as 16-bit words (column tap * c + ch of the first c channels)"""
+    words = x.view(torch.int16)[..., :c].permute(0, 3, 1, 2)
+    return _pack_rows(_taps(words), 1).view(x.dtype)
+
+
+def _cfg_coefs(sigma, ptype, sigma_data, dtype, plant=None):
+    """A, B [b, 1, 1, 1] of calculate_denoised in `dtype`, in the kernel's order of operations"""
+    s = sigma.to(dtype).view(-1, 1, 1, 1)
+    if ptype == "epsilon":
+        return torch.ones_like(s), -s
+    sd = torch.tensor(f32(sigma_data), dtype=dtype)
+    v = s * s + sd * sd
+    ca = (torch.ones((), dtype=dtype) if plant == "no_sd2_in_a" else sd * sd) / v
+    sign = 1.0 if (ptype == "edm") != (plant == "edm_sign") else -1.0
+    return ca, sign * s * sd / torch.sqrt(v)
+
+
+def _cfg_eps(eps, b, c, reps, plant=None):
+    """eps fp16 [reps * b, h, w, ld] -> (eu, ec) [b, c, h, w] (eu None with one half).  plant "ld_as_c": rows stepped c apart; "eps_nchw": the buffer
+    read as [reps * b, c, h, w]; "halves_swapped" """
+    n, h, w, ld = eps.shape
+    if plant == "ld_as_c":
+        e = eps.reshape(-1)[:n * h * w * c].view(n, h, w, c).permute(0, 3, 1, 2)
+    elif plant == "eps_nchw":
+        e = eps.reshape(-1)[:n * h * w * c].view(n, c, h, w)
+    else:
+        e = eps[..., :c].permute(0, 3, 1, 2)
+    if reps == 1:
+        return None, e[:b]
+    return (e[b:], e[:b]) if plant == "halves_swapped" else (e[:b], e[b:])
+
+
+def cfg_combine_ref(eps, x, sigma, reps, cond_scale, ptype="epsilon", sigma_data=1.0):
+    """fmx_cfg_combine in fp64: eps fp16 [reps * b, h, w, ld_eps] ([uncond ; cond]), x fp32 [b, c, h, w], sigma fp32 [b] ->
+    (denoised, cond_pred, uncond_pred, bound of denoised, bound of cond_pred, bound of uncond_pred); uncond_pred is 0 with one half"""
+    b, c = x.shape[:2]
+    cs = f32(cond_scale)
+    ca, cb = _cfg_coefs(sigma, ptype, sigma_data, torch.float64)
+    eu, ec = _cfg_eps(eps.double(), b, c, reps)
+    ax = ca * x.double()
+    dc = ax + cb * ec
+    tc = ax.abs() + (cb * ec).abs()
+    if reps == 1:
+        den, du, tu = cs * dc, torch.zeros_like(dc), torch.zeros_like(dc)
+        mag = tc + den.abs()
+    else:
+        du = ax + cb * eu
+        tu = ax.abs() + (cb * eu).abs()
+        den = du + cs * (dc - du)
+        mag = tu + tc + (cs * (dc - du)).abs()
+    return den, dc, du, CFG_R * U32 * mag, CFG_PRED_R * U32 * tc, CFG_PRED_R * U32 * tu
+
+
+def cfg_combine_emul(eps, x, sigma, reps, cond_scale, ptype="epsilon", sigma_data=1.0, plant=None):
+    """the kernel's formula in fp32 torch -> (denoised, cond_pred, uncond_pred).  plant: None, "halves_swapped", "preds_swapped" (cond_pred and uncond_pred
+    exchanged), "edm_sign" (the other sign of B on v_prediction / edm), "no_sd2_in_a" (A = 1 / (sigma^2 + sd^2): has teeth only at sigma_data != 1),
+    "ld_as_c", "eps_nchw" """
+    b, c = x.shape[:2]
+    cs = torch.tensor(f32(cond_scale), dtype=torch.float32)
+    ca, cb = _cfg_coefs(sigma, ptype, sigma_data, torch.float32, plant)
+    eu, ec = _cfg_eps(eps, b, c, reps, plant)
+    xv = x.float()
+    half = (lambda e: xv - e.float() * sigma.float().view(-1, 1, 1, 1)) if ptype == "epsilon" else (lambda e: xv * ca + e.float() * cb)
+    dc = half(ec)
+    if reps == 1:
+        du = torch.zeros_like(dc)
+        den = 0.0 + (dc - 0.0) * cs
+    else:
+        du = half(eu)
+        den = du + (dc - du) * cs
+    return (den, du, dc) if plant == "preds_swapped" else (den, dc, du)
+
+
+def euler_step_ref(x, den, sigma, sigma_next, noise=None, noise_scale=0.0):
+    """fmx_sampler_euler_step in fp64 -> (x_out, bound)"""
+    step = (x.double() - den.double()) / f32(sigma) * (f32(sigma_next) - f32(sigma))
+    out, mag = x.double() + step, x.double().abs() + step.abs()
+    if noise is not None:
+        out, mag = out + noise.double() * f32(noise_scale), mag + (noise.double() * f32(noise_scale)).abs()
+    return out, EULER_R * U32 * mag
+
+
+def euler_step_emul(x, den, sigma, sigma_next, noise=None, noise_scale=0.0, plant=None):
+    """plant: None, "dt_sign" (sigma - sigma_next), "noise_before_scale" (the noise joins d before the product with dt)"""
+    sg, sn = torch.tensor(f32(sigma), dtype=torch.float32), torch.tensor(f32(sigma_next), dtype=torch.float32)
+    dt = sg - sn if plant == "dt_sign" else sn - sg
+    d = (x.float() - den.float()) / sg
+    if noise is not None and plant == "noise_before_scale":
+        return x.float() + (d + noise.float() * f32(noise_scale)) * dt
+    r = x.float() + d * dt
+    return r if noise is None else r + noise.float() * f32(noise_scale)
+
+
+def lincomb_ref(srcs, coefs):
+    """fmx_sampler_lincomb in fp64 -> (sum_k coefs[k] * srcs[k], bound with R = n_terms)"""
+    terms = [f32(c) * t.double() for c, t in zip(coefs, srcs)]
+    return sum(terms), len(terms) * U32 * sum(t.abs() for t in terms)
+
+
+def lincomb_emul(srcs, coefs, plant=None, out_before=None):
+    """left to right in fp32.  plant: None, "tail_unwritten" (the n % 4 elements behind the last full float4 keep what the destination held: out_before),
+    "coef_shift" (coefficient k applied to source k + 1, cyclically)"""
+    if plant == "coef_shift":
+        srcs = list(srcs[1:]) + list(srcs[:1])
+    r = f32(coefs[0]) * srcs[0].float()
+    for c, t in zip(coefs[1:], srcs[1:]):
+        r = r + f32(c) * t.float()
+    if plant == "tail_unwritten":
+        full = (r.numel() // 4) * 4
+        r = r.clone()
+        r.view(-1)[full:] = out_before.float().view(-1)[full:]
+    return r
+
+
+def lincomb3_ref(x, d0, d1, a, b, c):
+    """fmx_sampler_lincomb3 in fp64 -> (a x + b d0 + c d1, bound); d1 None: two terms"""
+    terms = [f32(a) * x.double(), f32(b) * d0.double()] + ([] if d1 is None else [f32(c) * d1.double()])
+    return sum(terms), LINCOMB3_R * U32 * sum(t.abs() for t in terms)
+
+
+def lincomb3_emul(x, d0, d1, a, b, c):
+    if d1 is None:
+        return f32(a) * x.float() + f32(b) * d0.float()
+    return f32(a) * x.float() + (f32(b) * d0.float() + f32(c) * d1.float())
+
+
+def error_norm_rel_bound(n):
+    depth = -(-n // 65536) + 6 + 4 + 256
+    return 0.5 * (ERRNORM_TERM_R + depth) * U32
+
+
+def error_norm_ref(x_low, x_high, x_prev, atol, rtol):
+    """fmx_sampler_error_norm in fp64 -> python float; delta is formed from the fp32 atol / rtol"""
+    lo = x_low.double().reshape(-1)
+    delta = torch.clamp_min(f32(rtol) * torch.maximum(lo.abs(), x_prev.double().reshape(-1).abs()), f32(atol))
+    return float((((lo - x_high.double().reshape(-1)) / delta) ** 2).sum().sqrt() / math.sqrt(lo.numel()))
+
+
+def error_norm_emul(x_low, x_high, x_prev, atol, rtol, plant=None):
+    """the two kernels in fp32 torch IN THEIR SUMMATION ORDER (256 blocks of 256 threads, element i on thread i % 65536; strided per-thread sums, the
+    shuffle tree of a 64-lane wave, 4 waves and then 256 partials in sequence) -> python float.  plant: None, "prev_ignored" (|x_prev| not in the max),
+    "last_block_dropped" (the n % 256 elements behind the last full block of 256 never summed), "div_n" (the root divided by n, not sqrt(n))"""
+    lo, hi, pv = (t.float().reshape(-1) for t in (x_low, x_high, x_prev))
+    n = lo.numel()
+    big = lo.abs() if plant == "prev_ignored" else torch.maximum(lo.abs(), pv.abs())
+    delta = torch.clamp_min(f32(rtol) * big, f32(atol))
+    r = (lo - hi) / delta
+    sq = r * r
+    if plant == "last_block_dropped":
+        sq = sq[:(n // 256) * 256]
+    k = -(-max(sq.numel(), 1) // 65536)
+    sq = F.pad(sq, (0, k * 65536 - sq.numel())).view(k, 256, 4, 64)
+    acc = torch.zeros(256, 4, 64)
+    for i in range(k):
+        acc = acc + sq[i]
+    for off in (32, 16, 8, 4, 2, 1):                    # lane l adds lane l + off; lanes past the end read their own value, lane 0 never does
+        acc = acc + torch.cat([acc[..., off:], acc[..., -off:]], -1)
+    waves = acc[..., 0]
+    part = torch.zeros(256)
+    for w in range(4):
+        part = part + waves[:, w]
+    t = torch.zeros(())
+    for blk in range(256):
+        t = t + part[blk]
+    inv = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(n), dtype=torch.float32)
+    return float(torch.sqrt(t) * inv) if plant == "div_n" else float(torch.sqrt(t) * torch.sqrt(inv))
+
+
+def philox_raw_ref(seed, offset, n, plant=None):
+    """the four Philox4x32-10 words of elements 0 .. n - 1 (oracle/rng.py: key = the seed's two words, counter = (offset, 0, index, 0)) -> uint32 [n, 4].
+    plant: None, "seed_hi_ignored" (key word 1 = 0), "offset_in_word1" (counter = (0, offset, index, 0))"""
+    from oracle.rng import philox4x32_10
+    idx, z = np.arange(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+    off = np.full(n, offset & 0xFFFFFFFF, dtype=np.uint32)
+    k0 = np.full(n, seed & 0xFFFFFFFF, dtype=np.uint32)
+    k1 = z if plant == "seed_hi_ignored" else np.full(n, (seed >> 32) & 0xFFFFFFFF, dtype=np.uint32)
+    c = (z, off, idx, z) if plant == "offset_in_word1" else (off, z, idx, z)
+    return np.stack(philox4x32_10(*c, k0, k1), 1)

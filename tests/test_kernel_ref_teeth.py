@@ -1,5 +1,5 @@
 """CPU: the kernel-level GPU tests have teeth.  For each test in tests/test_gpu_kernels_bf16.py, tests/test_gpu_small_kernels.py, each test
-family of tests/test_gpu_attention_generic.py, each window case of tests/test_gpu_gemm_windows.py and each check of tests/test_gpu_vae_direct.py, one
+family of tests/test_gpu_attention_generic.py, each window case of tests/test_gpu_gemm_windows.py, each check of tests/test_gpu_vae_direct.py and each kernel of tests/test_gpu_sampler_kernels.py, one
 plausible subtle bug is planted into the fp64 reference (tests/kernel_refs.py) and evaluated on that test's own inputs; the planted result must
 lie outside the GPU test's tolerance by at least 4x (kernel_refs.excess >= 4), or -- for the exact tests -- differ in at least 4 places.
 Runs without a GPU, so a tolerance too loose to catch anything fails before anyone gets a GPU."""
@@ -856,3 +856,202 @@ def test_fast_attention_stores_outside_the_window_trip_the_sentinel_rule(dtype):
                 spill[at:at + 8] = 0.5
                 got = A._view(spill, L, "o", L.nq).permute(0, 2, 1, 3)
                 assert R.excess(got, want, dtype, *R.ATTN_TOL[dtype]) >= TEETH
+
+
+# ---- the sampler-step kernels (tests/test_gpu_sampler_kernels.py) ---------------------------------------------------------------------------------
+# The emulations of kernel_refs (the kernels' formulas in plain fp32 torch) run on every case of the GPU file: unplanted they stay inside the derived
+# bound (worst excess printed: the table beside the bounds in kernel_refs.py), with one bug planted they leave it by >= 4x; the bit-exact checks see >= 4
+# differing elements.
+import numpy as np  # noqa: E402
+
+import test_gpu_sampler_kernels as K  # noqa: E402
+
+
+def _report(kernel, worst):
+    print(f"EMULATION {kernel}: {worst:.3f}")
+    assert worst <= 1.0, f"{kernel}: the unplanted fp32 emulation is {worst:.3g}x the derived bound"
+
+
+def _bites_abs(planted, want, bound, what):
+    e = R.excess_abs(planted, want, bound)
+    assert e >= TEETH, f"{what}: the planted bug is only {e:.3g}x the bound"
+
+
+def test_sampler_windows_are_aligned_and_surrounded():
+    """condition of the GPU file: every window starts on a 16-byte boundary of its buffer and has surroundings on both sides"""
+    wins = list(K.pack_case(0)[:2]) + [K.im2col_case(0, BF)] + list(K.cfg_case(2, 3, 3)) + list(K.step_case(3)) + K.lincomb_case(5) + list(K.errnorm_case(257, "mixed"))
+    wins += [K.Out((5,), torch.float32, 2, 1), K.Out((7, 64), H16, 3, 2)]
+    for w in wins:
+        assert (w.lead * w.buf.element_size()) % 16 == 0 and w.lead > 0 and w.buf.numel() > w.lead + w.n
+        assert w.values.is_contiguous() and w.values.data_ptr() % 16 == w.buf.data_ptr() % 16
+
+
+def test_sampler_pack_input_emulation_and_planted_bugs():
+    worst = 0.0
+    for i in range(len(K.PACK_SHAPES)):
+        x, sigma, reps = K.pack_case(i)
+        for sd in K.SIGMA_DATAS:
+            want = R.pack_input_ref(x.values, sigma.values, sd, reps)
+            worst = max(worst, R.excess(R.pack_input_emul(x.values, sigma.values, sd, reps), want, H16, *R.ELEM_TOL[H16]))
+            plants = ["kykx", "sd2_dropped"] + (["ch_major"] if x.shape[1] > 1 else []) + (["sigma_of_image0"] if x.shape[0] > 1 else [])
+            if x.shape[2] == 1:
+                plants.remove("kykx")      # one pixel: only the centre tap is inside the image
+            for plant in plants:
+                bites(R.pack_input_emul(x.values, sigma.values, sd, reps, plant), want, H16, R.ELEM_TOL[H16], f"pack {K.PACK_SHAPES[i]} sd {sd} {plant}")
+            e = R.excess(R.pack_input_emul(x.values, sigma.values, sd, reps, "sd_not_squared"), want, H16, *R.ELEM_TOL[H16])
+            assert e >= TEETH if sd != 1.0 else e <= 1.0, f"sigma_data not squared at sigma_data {sd}: {e:.3g}"      # has teeth only away from 1
+    _report("unet_pack_input", worst)
+
+
+def test_sampler_im2col_planted_bugs_are_caught():
+    for i in range(len(K.IM2COL_SHAPES)):
+        n, h, w, c, ldx = K.IM2COL_SHAPES[i]
+        for dtype in DTS:
+            x = K.im2col_case(i, dtype).values
+            want = R.im2col_smallc_ref(x, c).view(torch.int16)
+            assert not bool((want == x.new_tensor(30000.0).view(torch.int16)).any())      # the padding channels never appear
+            dense = x.reshape(-1)[:n * h * w * c].view(n, h, w, c)                         # ldx taken as c
+            if ldx != c and n * h * w > 1:
+                assert int((R.im2col_smallc_ref(dense, c).view(torch.int16) != want).sum()) >= TEETH
+            if h > 1:                                                                       # ky / kx transposed
+                t = R._pack_rows(R._taps(x.view(torch.int16)[..., :c].permute(0, 3, 1, 2), transposed=True), 1)
+                assert int((t != want).sum()) >= TEETH
+            through_float = R._pack_rows(R._taps(x.float()[..., :c].permute(0, 3, 1, 2)), 1).to(dtype).view(torch.int16)
+            assert bool((through_float == want).all())                                      # (the reference moves words; the values agree)
+
+
+def _cfg_all():
+    for ptype in K.PTYPES:
+        for reps in (1, 2):
+            for sd in K.SIGMA_DATAS:
+                for c, ld in K.CFG_GEOS:
+                    for cs in K.COND_SCALES:
+                        eps, x, sigma = K.cfg_case(reps, c, ld)
+                        yield (ptype, reps, sd, c, ld, cs), (eps.values, x.values, sigma.values, reps, cs, ptype, sd)
+
+
+def test_sampler_cfg_combine_emulation_meets_the_bounds_on_every_case():
+    worst = {"denoised": 0.0, "preds": 0.0}
+    for key, args in _cfg_all():
+        den, dc, du, b_den, b_c, b_u = R.cfg_combine_ref(*args)
+        g_den, g_c, g_u = R.cfg_combine_emul(*args)
+        worst["denoised"] = max(worst["denoised"], R.excess_abs(g_den, den, b_den))
+        worst["preds"] = max(worst["preds"], R.excess_abs(g_c, dc, b_c))
+        if args[3] == 2:
+            worst["preds"] = max(worst["preds"], R.excess_abs(g_u, du, b_u))
+        else:
+            assert not bool(g_u.any()) and not bool(du.any())
+    _report("cfg_combine denoised", worst["denoised"])
+    _report("cfg_combine preds", worst["preds"])
+
+
+def test_sampler_cfg_combine_planted_bugs_are_caught():
+    """halves swapped, cond_pred <-> uncond_pred, the EDM sign on v_prediction (and the reverse), sigma_data^2 missing from A (teeth only at sigma_data 0.5:
+    at 1.0 the planted emulation is asserted to PASS), ld_eps taken as c, eps indexed as NCHW"""
+    for key, args in _cfg_all():
+        ptype, reps, sd, c, ld, cs = key
+        den, dc, du, b_den, b_c, b_u = R.cfg_combine_ref(*args)
+        plant = lambda p: R.cfg_combine_emul(*args, plant=p)  # noqa: E731
+        if reps == 2:
+            if cs != 0.5:         # (at 0.5 the combination is symmetric in the halves; not among the cases)
+                _bites_abs(plant("halves_swapped")[0], den, b_den, f"{key} halves swapped")
+            _bites_abs(plant("preds_swapped")[1], dc, b_c, f"{key} cond_pred <- uncond_pred")
+            _bites_abs(plant("preds_swapped")[2], du, b_u, f"{key} uncond_pred <- cond_pred")
+        if ptype != "epsilon":
+            _bites_abs(plant("edm_sign")[1], dc, b_c, f"{key} the other prediction type's sign")
+            e = R.excess_abs(plant("no_sd2_in_a")[1], dc, b_c)
+            assert e >= TEETH if sd != 1.0 else e <= 1.0, f"{key} sigma_data^2 missing from A: {e:.3g}"
+            if cs != 0.0 or reps == 2:
+                e = R.excess_abs(plant("no_sd2_in_a")[0], den, b_den)
+                assert e >= TEETH if sd != 1.0 else e <= 1.0, f"{key} sigma_data^2 missing from A (denoised): {e:.3g}"
+        if ld != c:
+            _bites_abs(plant("ld_as_c")[1], dc, b_c, f"{key} ld_eps taken as c")
+        _bites_abs(plant("eps_nchw")[1], dc, b_c, f"{key} eps indexed as NCHW")
+
+
+def test_sampler_euler_and_lincomb3_emulation_and_planted_bugs():
+    worst = {"euler_step": 0.0, "lincomb3": 0.0}
+    for n in K.STEP_NS:
+        x, den, old, noise = (w.values for w in K.step_case(n))
+        for sigma, sigma_next in K.EULER_STEPS:
+            for ns in K.EULER_NOISE:
+                nz = None if ns is None else noise
+                want, bound = R.euler_step_ref(x, den, sigma, sigma_next, nz, ns or 0.0)
+                worst["euler_step"] = max(worst["euler_step"], R.excess_abs(R.euler_step_emul(x, den, sigma, sigma_next, nz, ns or 0.0), want, bound))
+                _bites_abs(R.euler_step_emul(x, den, sigma, sigma_next, nz, ns or 0.0, plant="dt_sign"), want, bound, f"euler n {n} {sigma} dt sign")
+                if nz is not None:
+                    _bites_abs(R.euler_step_emul(x, den, sigma, sigma_next, nz, ns, plant="noise_before_scale"), want, bound, f"euler n {n} {sigma} noise first")
+        for a, b, c, has_old in K.LINCOMB3_COEFS:
+            want, bound = R.lincomb3_ref(x, den, old if has_old else None, a, b, c)
+            worst["lincomb3"] = max(worst["lincomb3"], R.excess_abs(R.lincomb3_emul(x, den, old if has_old else None, a, b, c), want, bound))
+            _bites_abs(R.lincomb3_emul(den, x, old if has_old else None, a, b, c), want, bound, f"lincomb3 n {n} x and denoised exchanged")
+            if has_old and c != 0.0:
+                _bites_abs(R.lincomb3_emul(x, den, None, a, b, c), want, bound, f"lincomb3 n {n} old_denoised dropped")
+    for k, e in worst.items():
+        _report(k, e)
+
+
+def test_sampler_lincomb_emulation_and_planted_bugs():
+    worst = 0.0
+    for n in K.LINCOMB_NS:
+        srcs = [w.values for w in K.lincomb_case(n)]
+        sentinel = K.Out((n,), torch.float32).values
+        for name, coefs in K.LINCOMB_COEFS.items():
+            for k in range(1, 9):
+                want, bound = R.lincomb_ref(srcs[:k], coefs[:k])
+                worst = max(worst, R.excess_abs(R.lincomb_emul(srcs[:k], coefs[:k]), want, bound))
+                if n % 4:      # the scalar tail behind the last full float4 left unwritten: into a fresh destination, and in place on source 0
+                    _bites_abs(R.lincomb_emul(srcs[:k], coefs[:k], "tail_unwritten", sentinel), want, bound, f"lincomb n {n} terms {k} {name} tail")
+                    if not (k == 1 and coefs[0] == 1.0):
+                        _bites_abs(R.lincomb_emul(srcs[:k], coefs[:k], "tail_unwritten", srcs[0]), want, bound, f"lincomb n {n} terms {k} {name} tail in place")
+                if k >= 2:
+                    _bites_abs(R.lincomb_emul(srcs[:k], coefs[:k], "coef_shift"), want, bound, f"lincomb n {n} terms {k} {name} coefficients shifted")
+    _report("lincomb", worst)
+
+
+def test_sampler_error_norm_emulation_and_planted_bugs():
+    worst = 0.0
+    for n in K.ERRNORM_NS:
+        rel = R.error_norm_rel_bound(n)
+        for kind in K.ERRNORM_KINDS:
+            lo, hi, pv = (w.values for w in K.errnorm_case(n, kind))
+            want = R.error_norm_ref(lo, hi, pv, K.ERR_ATOL, K.ERR_RTOL)
+            got = R.error_norm_emul(lo, hi, pv, K.ERR_ATOL, K.ERR_RTOL)
+            if kind == "equal":
+                assert want == 0.0 and got == 0.0
+                continue
+            worst = max(worst, abs(got - want) / (rel * want))
+            ex = lambda p: abs(R.error_norm_emul(lo, hi, pv, K.ERR_ATOL, K.ERR_RTOL, p) - want) / (rel * want)  # noqa: E731
+            if n > 1:
+                assert ex("div_n") >= TEETH, (n, kind, "div_n")
+            if kind == "mixed" and n >= 255:
+                assert ex("prev_ignored") >= TEETH, (n, kind, "prev_ignored")
+            if kind == "last_heavy":
+                last = ((hi[-1].double() - lo[-1].double()) / R.f32(K.ERR_ATOL)) ** 2 / n
+                assert last > 0.5 * want * want, "the last element does not carry most of the norm"
+                if n % 256:
+                    assert ex("last_block_dropped") >= TEETH, (n, kind, "last_block_dropped")
+    # both sides of max(atol, rtol * max(|lo|, |prev|)) are exercised, and x_prev decides on a good part of the elements
+    lo, hi, pv = (w.values for w in K.errnorm_case(65537, "mixed"))
+    rel_side = R.f32(K.ERR_RTOL) * torch.maximum(lo.abs(), pv.abs()) > R.f32(K.ERR_ATOL)
+    assert 0.2 < float(rel_side.float().mean()) < 0.8 and float((pv.abs() > lo.abs()).float().mean()) > 0.3
+    _report("error_norm", worst)
+
+
+def test_sampler_philox_planted_bugs_are_caught():
+    """the high seed word ignored; the offset placed in counter word 1 -- on the seeds and offsets of the GPU file"""
+    hi_seed = [s for s in K.PHILOX_SEEDS if s >> 32]
+    assert hi_seed and 0 in K.PHILOX_OFFSETS and 2 ** 32 - 1 in K.PHILOX_OFFSETS
+    for n in K.PHILOX_NS:
+        for seed in hi_seed:
+            for offset in K.PHILOX_OFFSETS:
+                want = R.philox_raw_ref(seed, offset, n)
+                assert int((R.philox_raw_ref(seed, offset, n, "seed_hi_ignored") != want).sum()) >= TEETH
+                if offset:
+                    assert int((R.philox_raw_ref(seed, offset, n, "offset_in_word1") != want).sum()) >= TEETH
+    # the reference agrees with the project's own Philox restatement and its known-answer route (oracle/rng.py philox_randn uses the same words)
+    from oracle.rng import philox_randn
+    raw = R.philox_raw_ref(K.PHILOX_SEEDS[0], 7, 257).astype(np.float32)
+    inv = np.float32(2.3283064e-10)
+    u, v = raw[:, 0] * inv + inv / 2, raw[:, 1] * np.float32(2.3283064e-10 * 6.2831855) + np.float32(2.3283064e-10 * 6.2831855) / 2
+    np.testing.assert_allclose(np.sqrt(-2.0 * np.log(u)) * np.sin(v), philox_randn(K.PHILOX_SEEDS[0], 7, 257), rtol=0, atol=1e-6)
