@@ -52,6 +52,7 @@
  *   fmx_bnb4_dequant_*     backend/memory_management.py:311-337 (state_dict_dtype), backend/operations_bnb.py (ForgeParams4bit, functional_linear_4bits),
  *                          backend/operations.py:353-389 (the manual cast of fp8-stored weights)
  *   fmx_freeu_*            FreeU v2 extensions-builtin/sd_forge_freeu/scripts/forge_freeu.py:9-58 (Fourier_filter, output_block_patch)
+ *   fmx_resize_nhwc_f16    Kohya HRFix extensions-builtin/sd_forge_kohya_hrfix/scripts/kohya_hrfix.py:13-28 (input_block_patch, output_block_patch)
  *   fmx_row_abs_quantile_f32 / fmx_dynthresh_f32
  *                          Dynamic Thresholding (CFG-Fix) extensions-builtin/sd_forge_dynamic_thresholding/lib_dynamic_thresholding/dynthres_core.py:61-125
  */
@@ -668,6 +669,24 @@ int fmx_freeu_apply_f16(void* h, int32_t c_h, void* skip, int32_t c_s, int32_t n
 int fmx_row_abs_quantile_f32(const float* x, const float* center, int32_t rows, int32_t n, int32_t rows_per_group, float q, float* out, void* stream);
 int fmx_dynthresh_f32(const float* cond, const float* uncond, int32_t b, int32_t c, int32_t hw, float mimic, float cfg, float percentile,
                       int32_t flags, double phi, float* workspace, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * NHWC resize: the separable resize of a channels-last fp16 activation -- what "Kohya HRFix Integrated" (Deep Shrink,
+ * extensions-builtin/sd_forge_kohya_hrfix/scripts/kohya_hrfix.py:13-28, through backend/misc/image_resize.py adaptive_resize) does to the UNet's
+ * hidden state after one input block and undoes at the first output block whose skip tensor is larger.
+ * New symbol only: no existing signature moves, the ABI number stays 12.
+ *   in  : fp16 [n][h][w][c], contiguous;   out : fp16 [n][oh][ow][c], contiguous
+ *   out[b, oy, ox, ch] = sum_i sum_j yweights[oy, i] * xweights[ox, j] * in[b, ystart[oy] + i, xstart[ox] + j, ch]     (i < ky, j < kx)
+ * The tables are those of fmx_resize_separable_f32 (modules/latent_upscale.py axis_table: bicubic, bilinear, nearest-exact, area, ...):
+ *   ystart [oh] int32, yweights [oh][ky] fp32, xstart [ow] int32, xweights [ow][kx] fp32, on the device; border taps are folded by the
+ *   caller, so ystart[oy] + i < h and xstart[ox] + j < w for every tap (the kernel does not clamp).
+ * fp32 accumulation, rows outer and columns inner (the weight of a tap is yweights * xweights rounded once), one fp16 rounding at the store;
+ * no atomics, no LDS: the same bits on every run.  One lane owns 8 consecutive channels of one output pixel (16-byte loads and store).
+ * Requirements (FMX_E_BADARG otherwise, before any launch): every pointer non-null, in / out 16-byte aligned; n, h, w, c, oh, ow > 0;
+ * c % 8 == 0; 1 <= ky <= h, 1 <= kx <= w; n*h*w*c < 2^31 and n*oh*ow*c < 2^31.
+ * ---------------------------------------------------------------------------------------------- */
+int fmx_resize_nhwc_f16(const void* in, void* out, const int32_t* ystart, const float* yweights, const int32_t* xstart, const float* xweights,
+                        int32_t n, int32_t h, int32_t w, int32_t c, int32_t oh, int32_t ow, int32_t ky, int32_t kx, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * HIP-graph helpers: capture everything launched on `stream` between begin/end into an executable graph.

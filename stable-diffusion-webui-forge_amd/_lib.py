@@ -179,6 +179,9 @@ SIGNATURES["fmx_freeu_apply_f16"] = [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp
 # phi, workspace, out, stream): new symbols, the ABI number does not move
 SIGNATURES["fmx_row_abs_quantile_f32"] = [_vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp]
 SIGNATURES["fmx_dynthresh_f32"] = [_vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _i32, C.c_double, _vp, _vp, _vp]
+# NHWC fp16 resize of native Kohya HRFix (in, out, ystart, yweights, xstart, xweights, n, h, w, c, oh, ow, ky, kx, stream): a new symbol, the ABI
+# number does not move
+SIGNATURES["fmx_resize_nhwc_f16"] = [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]
 
 
 def source_tree_hash():

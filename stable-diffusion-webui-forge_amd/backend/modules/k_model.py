@@ -9,6 +9,7 @@ import torch
 
 from ... import hipops as ops
 from ...runtime import HipGraph
+from ..patcher.kohya_hrfix import shrink_for_step, shrink_graph_key
 
 
 class SigmaInfo:
@@ -87,11 +88,19 @@ class KModel:
         return entries
 
     def _forward_static(self, key, x, sigma_dev, sig_host, reps, ctxc, control=None, transformer_options=None, c_concat=None, control_plan=None,
-                        freeu=None):
+                        freeu=None, shrink=None):
         """pack -> [ControlNets ->] UNet -> (returns eps view); static buffers per shape so the chain can be graph-replayed.
         `freeu`: the job's native FreeU parameters (transformer_options["freeu_v2"], backend/patcher/freeu.py) or None.  They are launch
         arguments of the captured kernels, so they are part of the graph key: the steps inside and outside the FreeU window of one job
-        are two graphs."""
+        are two graphs.
+        `shrink`: the job's native Kohya HRFix parameters (transformer_options["kohya_hrfix"], backend/patcher/kohya_hrfix.py) when this step's
+        host sigma lies inside their window, else None.  A shrunk forward launches other kernels on other shapes, so it is part of the graph
+        key as well; a step outside the window replays the plain graph."""
+        if shrink is not None:
+            if freeu is not None:
+                raise NotImplementedError("Kohya HRFix and native FreeU on one job: FreeU needs h and the skip at one size, and the two do not commute")
+            if control is not None or any(e["active"] for e in control_plan or ()):
+                raise NotImplementedError("Kohya HRFix with ControlNet / T2I-Adapter residuals: their sizes do not fit the shrunk hidden state")
         b, c, hh, ww = x.shape
         bu = reps * b
         st = self._static.get(key)
@@ -115,11 +124,13 @@ class KModel:
         concat_term = net.prepare_concat(c_concat, bu) if c_concat is not None else None  # cached per c_concat tensor: once per job
         if not self.use_graph or control is not None or hooks is not None:
             # Python hooks cannot be captured, and a ControlNet chain that needs Python per step arrives here with its residuals: eager
-            return net.forward_packed(st["xcol"], st["t"], ctxc, bu, hh, ww, control, hooks, concat_term, freeu=freeu)
+            return net.forward_packed(st["xcol"], st["t"], ctxc, bu, hh, ww, control, hooks, concat_term, freeu=freeu, shrink=shrink)
         active = [e for e in control_plan if e["active"]] if control_plan else []
         gkey = key if not active else key + ("control",) + tuple(e["cm"].exec_serial for e in active)
         if freeu is not None:
             gkey = gkey + freeu_graph_key(freeu)
+        if shrink is not None:
+            gkey = gkey + shrink_graph_key(shrink)
 
         def run():
             # The ControlNet trunks read the SAME packed input and timestep buffers as the UNet (both are `calculate_input` of x and the
@@ -129,7 +140,7 @@ class KModel:
             for e in reversed(active):
                 outs = e["cm"].forward_static(st["xcol"], st["t"], e["ctxc"], bu, hh, ww, e["gh"])
                 ctrl = e["cn"].control_merge(None, outs, ctrl, torch.float32)
-            return net.forward_packed(st["xcol"], st["t"], ctxc, bu, hh, ww, control=ctrl, concat_term=concat_term, freeu=freeu)
+            return net.forward_packed(st["xcol"], st["t"], ctxc, bu, hh, ww, control=ctrl, concat_term=concat_term, freeu=freeu, shrink=shrink)
 
         def validity():
             # What a captured graph points at: the executors' arenas (re-allocated when a larger shape comes through, e.g. the hires pass),
@@ -188,6 +199,7 @@ class KModel:
         `transformer_options` with Python hooks: completed with the per-call keys of sampling_function.py:253-257 and run eagerly."""
         b, c, hh, ww = x.shape
         reps = 1 if uncond_ctx is None else 2
+        job_options = transformer_options
         freeu = (transformer_options or {}).get("freeu_v2")   # native, no Python hook: stays on the graph path
         if self.diffusion_model._hooks(transformer_options) is not None or control_model is not None:
             to = dict(transformer_options or {})
@@ -202,6 +214,7 @@ class KModel:
             transformer_options = None
         per_call_options = transformer_options
         sig_host = host_sigmas(sigma)
+        shrink = shrink_for_step(job_options, sig_host)    # native as well; the window is tested on the host's copy of sigma
         if reps == 2:
             ctx = self._stack_ctx(uncond_ctx, cond_ctx)
         else:
@@ -223,7 +236,7 @@ class KModel:
                 t_all.fmx_sigma = SigmaInfo(list(sig_host) * reps)
                 control = control_model.get_control(torch.cat([x] * reps), t_all, {"c_crossattn": ctx[0], "y": ctx[1]}, reps)
         eps = self._forward_static(key, x, sigma, sig_host, reps, ctxc, control=control, transformer_options=transformer_options, c_concat=c_concat,
-                                   control_plan=plan, freeu=freeu)
+                                   control_plan=plan, freeu=freeu, shrink=shrink)
         cond_pred = torch.empty_like(x) if want_parts else None
         uncond_pred = torch.empty_like(x) if want_parts else None
         den = ops.cfg_combine(eps, eps.shape[-1], x, sigma, reps, cond_scale, None, cond_pred, uncond_pred,
@@ -253,8 +266,9 @@ class KModel:
         sigma = t.to(device=self.device, dtype=torch.float32).contiguous()
         ctxc = self.diffusion_model.prepare_context(c_crossattn, y)
         b, c, hh, ww = x.shape
-        eps = self._forward_static((b, c, hh, ww, 1, "apply"), x, sigma, host_sigmas(t), 1, ctxc, control, transformer_options, c_concat,
-                                   freeu=(transformer_options or {}).get("freeu_v2"))
+        sig_host = host_sigmas(t)
+        eps = self._forward_static((b, c, hh, ww, 1, "apply"), x, sigma, sig_host, 1, ctxc, control, transformer_options, c_concat,
+                                   freeu=(transformer_options or {}).get("freeu_v2"), shrink=shrink_for_step(transformer_options, sig_host))
         return ops.cfg_combine(eps, eps.shape[-1], x, sigma, 1, 1.0, prediction_type=self.predictor.prediction_type,
                                sigma_data=self.predictor.sigma_data)
 
@@ -278,6 +292,8 @@ class KModelFlux:
     def apply_model(self, x, t, c_concat=None, c_crossattn=None, control=None, transformer_options=None, y=None, guidance=None, **kwargs):
         if (transformer_options or {}).get("freeu_v2") is not None:
             raise NotImplementedError("FreeU: UNet models only")   # the reference's script declines models without model_channels
+        if (transformer_options or {}).get("kohya_hrfix") is not None:
+            raise NotImplementedError("Kohya HRFix: UNet models only")
         if c_concat is not None or control is not None:
             raise NotImplementedError("c_concat / control are outside the txt2img hot path")
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
@@ -292,6 +308,8 @@ class KModelFlux:
         to = transformer_options or {}
         if to.get("freeu_v2") is not None:
             raise NotImplementedError("FreeU: UNet models only")
+        if to.get("kohya_hrfix") is not None:
+            raise NotImplementedError("Kohya HRFix: UNet models only")
         if control_model is not None or to.get("patches") or to.get("patches_replace") or to.get("block_modifiers"):
             raise NotImplementedError("ControlNet / per-block hooks are built for the LDM UNet executor, not for the Flux transformer")
         ctx, y, guidance = cond_ctx

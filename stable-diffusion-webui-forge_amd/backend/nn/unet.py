@@ -708,13 +708,24 @@ class IntegratedUNet2DConditionModel:
         self._concat_cache = (key, term, c_concat)
         return term
 
-    def _forward_impl(self, xcol, t, ctxc, bu, hh, ww, arena, control=None, to=None, concat_term=None, freeu=None):
+    def _forward_impl(self, xcol, t, ctxc, bu, hh, ww, arena, control=None, to=None, concat_term=None, freeu=None, shrink=None):
         """xcol: [Bu*H*W, 64] im2col of the (scaled) input; t: [Bu] fp32 table indices.  -> eps [Bu*H*W, out_ch].
         `to`: transformer_options with Python hooks (unet.py:696-763 hook points), or None on the fast path.
         `freeu`: a FreeUParams tuple (b1, b2, s1, s2, ...) of backend/patcher/freeu.py, or None: native FreeU v2 on the inputs of the
         output blocks whose h has 4x / 2x model_channels channels.  Not a Python hook: it runs on the fast path and inside a captured graph.  It
         runs where the reference's output_block_patch runs when FreeU is the first installed patch; a job that ALSO installs Python
-        output-block patches gets native FreeU first, then those patches, eagerly as before."""
+        output-block patches gets native FreeU first, then those patches, eagerly as before.
+        `shrink`: a KohyaHRFixParams tuple of backend/patcher/kohya_hrfix.py, or None: native Kohya HRFix (Deep Shrink).  After input block
+        `block_number` h is resized to round(extent / factor) -- after the skip is stored, or before it (downscale_after_skip False) -- and at every
+        output block whose popped skip has another height h is resized to the skip's size, where the reference's input_block_patch(_after_skip)
+        and output_block_patch run (kohya_hrfix.py:13-28).  Not a Python hook either: fast path, captured graph; Python patches of the same
+        job run after it.  The caller decides the sigma window (KModel hands the option over only inside it)."""
+        if shrink is not None:
+            if freeu is not None:
+                raise NotImplementedError("Kohya HRFix and native FreeU on one job: FreeU needs h and the skip at one size, and the two do not commute")
+            if control is not None and any(len(v) > 0 for v in control.values()):
+                # the reference prints a warning and drops the residuals whose size no longer fits; a silently dropped ControlNet is refused here
+                raise NotImplementedError("Kohya HRFix with ControlNet / T2I-Adapter residuals: their sizes do not fit the shrunk hidden state")
         freeu_scales = None
         if freeu is not None:
             b1, b2, s1, s2 = (float(v) for v in freeu[:4])
@@ -771,9 +782,13 @@ class IntegratedUNet2DConditionModel:
                 h = self._run_block(blk, h, None, emb_all, ctxc, arena, to=to)
             h = self._apply_control(h, control, "input")
             h = modify(h, "after")
+            if shrink is not None and bi == shrink.block_number and not shrink.downscale_after_skip:
+                h = self._shrink(h, shrink, f"input.{bi}.shrink")
             for p in patches.get("input_block_patch", []):
                 h = self._call_nchw(p, h, to)
             hs.append(h)
+            if shrink is not None and bi == shrink.block_number and shrink.downscale_after_skip:
+                h = self._shrink(h, shrink, f"input.{bi}.shrink")
             for p in patches.get("input_block_patch_after_skip", []):
                 h = self._call_nchw(p, h, to)
         if to is not None:
@@ -786,6 +801,9 @@ class IntegratedUNet2DConditionModel:
             if to is not None:
                 to["block"] = ("output", bi)
             skip = self._apply_control(hs.pop(), control, "output")
+            if shrink is not None and h.shape[1] != skip.shape[1]:
+                h = ops.resize_nhwc(h, (skip.shape[1], skip.shape[2]), shrink.upscale_method)
+                self._tap(f"output.{bi}.shrink", h)
             scale = freeu_scales.get(h.shape[-1]) if freeu_scales is not None else None
             if scale is not None:
                 mk = arena.mark()
@@ -836,6 +854,12 @@ class IntegratedUNet2DConditionModel:
             out = modify(out.view(bu, hh, ww, -1)[..., :oc].contiguous(), "after").reshape(bu * hh * ww, oc)
         return out
 
+    def _shrink(self, h, shrink, tap_name):
+        from ..patcher.kohya_hrfix import shrunk_size
+        h = ops.resize_nhwc(h, shrunk_size(h.shape[1], h.shape[2], shrink.downscale_factor), shrink.downscale_method)
+        self._tap(tap_name, h)
+        return h
+
     def _get_arena(self, bu, hh, ww):
         need = self._arena_bytes or max(1 << 28, 40 * bu * hh * ww * self.layout.model_channels * 2)
         if self._arena is None or self._arena.capacity < need:
@@ -845,15 +869,17 @@ class IntegratedUNet2DConditionModel:
             self.arena_epoch += 1
         return self._arena
 
-    def forward_packed(self, xcol, t, ctxc, bu, hh, ww, control=None, transformer_options=None, concat_term=None, freeu=None):
+    def forward_packed(self, xcol, t, ctxc, bu, hh, ww, control=None, transformer_options=None, concat_term=None, freeu=None, shrink=None):
         """Hot-path entry (no layout conversion): returns eps as fp16 [Bu*H*W, out_channels] living in the arena
-        (valid until the next forward).  `freeu`: see _forward_impl (the caller takes it out of transformer_options["freeu_v2"])."""
+        (valid until the next forward).  `freeu`, `shrink`: see _forward_impl (the caller takes them out of transformer_options["freeu_v2"] /
+        ["kohya_hrfix"])."""
         while True:
             arena = self._get_arena(bu, hh, ww)
             arena.reset()
             try:
                 with arena:
-                    return self._forward_impl(xcol, t, ctxc, bu, hh, ww, arena, control, self._hooks(transformer_options), concat_term, freeu)
+                    return self._forward_impl(xcol, t, ctxc, bu, hh, ww, arena, control, self._hooks(transformer_options), concat_term, freeu,
+                                              shrink)
             except ArenaOverflow:
                 torch.cuda.synchronize(self.device)
                 self._arena_bytes = arena.capacity * 2
@@ -891,7 +917,8 @@ class IntegratedUNet2DConditionModel:
             x = x[:, :self.latent_channels]
         xcol = ops.unet_pack_input(x.contiguous(), ones, 1, 1.0)
         eps = self.forward_packed(xcol, timesteps.to(device=self.device, dtype=torch.float32).contiguous(), ctxc, bu, hh, ww, control,
-                                  transformer_options, concat_term, freeu=(transformer_options or {}).get("freeu_v2"))
+                                  transformer_options, concat_term, freeu=(transformer_options or {}).get("freeu_v2"),
+                                  shrink=(transformer_options or {}).get("kohya_hrfix"))
         return eps.view(bu, hh, ww, -1).permute(0, 3, 1, 2).to(x.dtype)
 
     __call__ = forward

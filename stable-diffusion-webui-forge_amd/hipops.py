@@ -921,6 +921,40 @@ def resize_separable(x, ystart, yweights, xstart, xweights):
     return out
 
 
+RESIZE_NHWC_MODES = ("bicubic", "bilinear", "nearest-exact", "area")   # F.interpolate(mode=..., align_corners=False), no antialias
+_resize_tables = {}
+
+
+def resize_nhwc_tables(h, w, oh, ow, mode, device):
+    """-> (ystart, yweights, xstart, xweights) on the device, built once per (h, w, oh, ow, mode, device) from modules/latent_upscale.axis_table
+    and kept for the life of the process: the upload happens in an eager warm-up forward, and a captured graph keeps the addresses."""
+    key = (h, w, oh, ow, mode, device.type, device.index)
+    t = _resize_tables.get(key)
+    if t is None:
+        if mode not in RESIZE_NHWC_MODES:
+            raise ValueError(f"resize_nhwc: mode {mode!r} is not one of {RESIZE_NHWC_MODES}")
+        from .modules.latent_upscale import axis_table
+        ys, yw = axis_table(h, oh, mode, False)
+        xs, xw = axis_table(w, ow, mode, False)
+        t = _resize_tables[key] = tuple(v.contiguous().to(device) for v in (ys, yw, xs, xw))
+    return t
+
+
+def resize_nhwc(x, size, mode="bicubic"):
+    """x fp16 [N, H, W, C] contiguous NHWC -> a new [N, size[0], size[1], C]: F.interpolate(mode, align_corners=False) of the NCHW view, or
+    adaptive_avg_pool2d for "area" (include/fmx.h, section "NHWC resize").  The result carries no GroupNorm statistics."""
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError(f"resize_nhwc expects a contiguous NHWC tensor, got {tuple(x.shape)} with strides {x.stride()}")
+    _check_f16(x)
+    n, h, w, c = x.shape
+    oh, ow = int(size[0]), int(size[1])
+    ys, yw, xs, xw = resize_nhwc_tables(h, w, oh, ow, mode, x.device)
+    out = empty((n, oh, ow, c), torch.float16, x.device)
+    _lib.check(_lib.lib().fmx_resize_nhwc_f16(_p(x), _p(out), _p(ys), _p(yw), _p(xs), _p(xw), n, h, w, c, oh, ow, yw.shape[1], xw.shape[1],
+                                              stream_ptr()), "fmx_resize_nhwc_f16")
+    return out
+
+
 def scale_f32(x, s, out=None):
     if out is None:
         out = torch.empty_like(x)

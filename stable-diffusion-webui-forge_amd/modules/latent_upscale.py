@@ -1,6 +1,7 @@
 """Latent resize for the hires-fix pass -- what `torch.nn.functional.interpolate(samples, size, mode, antialias)` computes at
 modules/processing.py:1459 for the modes of shared.latent_upscale_modes (modules/shared.py:55-63: bilinear, bicubic, nearest,
-nearest-exact, with and without antialias), align_corners=False.
+nearest-exact, with and without antialias), align_corners=False.  `axis_table` also knows "area" (adaptive_avg_pool2d), which the hires pass
+does not offer: the NHWC resize of native Kohya HRFix (hipops.resize_nhwc) takes its tables from here.
 
 Every one of those modes is separable and linear: out[o] = sum_k w[o, k] * in[start[o] + k] per axis.  The (start, weights) tables
 are a few hundred host floats built here the way ATen builds them (area_pixel source index for the plain modes; the
@@ -59,6 +60,11 @@ def axis_table(n_in, n_out, mode, antialias):
             total = F(sum(ws, F(0)))
             for j, w in enumerate(ws):
                 add(lo + j, w / total if total != 0.0 else F(0))
+        elif mode == "area":
+            # adaptive_avg_pool2d (what F.interpolate's "area" is): the window floor(o * in / out) .. ceil((o + 1) * in / out), equal weights
+            first, last = (o * n_in) // n_out, -((-(o + 1) * n_in) // n_out)
+            for i in range(first, last):
+                add(i, F(1) / F(last - first))
         elif mode == "nearest":
             add(min(int(np.floor(F(o) * scale)), n_in - 1), 1.0)
         elif mode == "nearest-exact":

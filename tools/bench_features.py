@@ -7,6 +7,8 @@ batch sizes -- and what they cost.
     python tools/bench_features.py [--steps 6] [--only samplers,controlnet,hooks,freeu,and,hires]
     python tools/bench_features.py --only dynthresh  Dynamic Thresholding: plain / native at percentile 1.0 and 0.99 / the same arithmetic as a Python
                                                      sampler_cfg_function, interleaved in one process, device events around every job
+    python tools/bench_features.py --only kohya      Kohya HRFix: plain / native (transformer option, captured graph) / the same arithmetic as the
+                                                     reference's Python patches (eager), interleaved in one process, device events around every job
     python tools/bench_features.py --only taesd      the TAESD decode of batch x (res/8)^2 SDXL-shaped latents (synthetic weights, fp16) next to the Full
                                                      VAE decode of the same latents in the same process: median of 5 after warm-up, events around the calls
 """
@@ -249,12 +251,85 @@ def main():
                           "hooked_minus_native_ms": {p_: round(med["hooked_" + p_] - med["native_" + p_], 2) for p_ in ("p1.0", "p0.99")},
                           "dynthresh_op_ms": op_ms, "finite": finite, "shape": list(lat.shape)}), flush=True)
 
+    def kohya_leg(rounds=5, block_number=3, factor=2.0, method="bicubic"):
+        """Plain, native Kohya HRFix (transformer option, captured graph) and the same arithmetic as the reference's Python patches
+        (tests/kohya_refs.py: F.interpolate in fp32 and the device read of sigma, on the eager hooked executor), after-skip, the window open for
+        every step so that every timed step is a shrunk one -- primed once each, then timed alternately, `rounds` jobs of a.steps steps per
+        variant in this one process, device events around each job.  Also the resize launches of one UNet call on their own (events, median
+        of 20): what the native route adds to a shrunk forward."""
+        import kohya_refs as kr
+        from forge_amd import hipops as ops
+        from forge_amd.backend.patcher import kohya_hrfix as pk
+        native = pk.patch_kohya_hrfix(eng.forge_objects.unet, block_number, factor, 0.0, 1.0, True, method, method)
+        prm = native.model_options["transformer_options"]["kohya_hrfix"]
+        ip, op = kr.python_patches(block_number, factor, prm.sigma_start, prm.sigma_end, method, method)
+        hooked = eng.forge_objects.unet.clone()
+        hooked.set_model_input_block_patch_after_skip(ip)
+        hooked.set_model_output_block_patch(op)
+        variants = {"plain": None, "kohya_native": native, "kohya_hooked": hooked}
+        shapes = []                       # (input shape, size, mode) of every ops.resize_nhwc call
+        real = ops.resize_nhwc
+        ops.resize_nhwc = lambda x, size, mode="bicubic": (shapes.append((tuple(x.shape), tuple(size), mode)), real(x, size, mode))[1]
+        saved = eng.forge_objects_after_applying_lora
+
+        def once(unet, n):
+            if unet is not None:
+                eng.forge_objects_after_applying_lora = saved.shallow_copy()
+                eng.forge_objects_after_applying_lora.unet = unet
+            try:
+                pr = processing.StableDiffusionProcessingTxt2Img(sd_model=eng, c=c1, uc=u1, seed=1, sampler_name="Euler", batch_size=b, steps=n,
+                                                                 cfg_scale=7.0, width=width, height=height, do_decode=False)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                lat = processing.process_images(pr).latents
+                e1.record()
+                torch.cuda.synchronize()
+                return e0.elapsed_time(e1), lat
+            finally:
+                eng.forge_objects_after_applying_lora = saved
+                eng.forge_objects = saved.shallow_copy()
+        try:
+            for unet in variants.values():    # priming (arena, caches, graphs)
+                once(unet, 4)
+        finally:
+            ops.resize_nhwc = real
+        per_call = shapes[:2]                 # one UNet call: the shrink after the input block, the resize back at one output block
+        ms = {k: [] for k in variants}
+        finite = True
+        for _ in range(rounds):
+            for k, unet in variants.items():
+                once(unet, 2)             # a job on another route came before: what follows a change of route is not timed
+                dt, lat = once(unet, a.steps)
+                ms[k].append(round(dt / a.steps, 2))
+                finite = finite and bool(torch.isfinite(lat).all())
+        med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+        bufs = [(torch.randn(s[0], device=dev).half(), s[1], s[2]) for s in per_call]
+        kern = []
+        for i in range(23):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for args in bufs:
+                ops.resize_nhwc(*args)
+            e1.record()
+            torch.cuda.synchronize()
+            if i >= 3:
+                kern.append(e0.elapsed_time(e1))
+        print(json.dumps({"case": f"Kohya HRFix (block {block_number}, factor {factor}, after skip, {method}, window open on every step): plain vs native "
+                                  "(captured graph) vs hooked (Python input / output block patches, eager)", "sampler": "Euler", "steps": a.steps,
+                          "rounds": rounds, "ms_per_step": med, "ms_per_step_rounds": ms, "native_minus_plain_ms": round(med["kohya_native"] - med["plain"], 2),
+                          "hooked_minus_native_ms": round(med["kohya_hooked"] - med["kohya_native"], 2),
+                          "resize_calls_per_unet_call": [[list(s[0]), list(s[1]), s[2]] for s in per_call],
+                          "resize_kernels_ms_per_unet_call": round(sorted(kern)[len(kern) // 2], 4), "finite": finite, "shape": list(lat.shape)}), flush=True)
+
     if "one" in what:
         run(f"{width}x{height}", sampler="Euler")
     if "dynthresh" in what:
         dynthresh_leg()
     if "freeu" in what:
         freeu_leg()
+    if "kohya" in what:
+        kohya_leg()
     if "samplers" in what:
         for s in ("Euler", "Euler a", "DPM++ 2M", "Heun", "DPM2 a", "DPM++ 2S a", "LMS", "IPNDM_V", "DEIS", "DPM++ SDE", "DPM++ 2M SDE", "DPM++ 3M SDE",
                   "DPM fast", "DDIM", "PLMS", "UniPC", "LCM", "DDPM"):
