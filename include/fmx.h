@@ -53,6 +53,9 @@
  *                          backend/operations.py:353-389 (the manual cast of fp8-stored weights)
  *   fmx_freeu_*            FreeU v2 extensions-builtin/sd_forge_freeu/scripts/forge_freeu.py:9-58 (Fourier_filter, output_block_patch)
  *   fmx_resize_nhwc_f16    Kohya HRFix extensions-builtin/sd_forge_kohya_hrfix/scripts/kohya_hrfix.py:13-28 (input_block_patch, output_block_patch)
+ *   fmx_attn_value_rows_f16 / fmx_cfg_pag_combine
+ *                          PerturbedAttentionGuidance extensions-builtin/sd_forge_perturbed_attention/scripts/forge_perturbed_attention.py:62-83
+ *                          (attn_proc, post_cfg_function)
  *   fmx_row_abs_quantile_f32 / fmx_dynthresh_f32
  *                          Dynamic Thresholding (CFG-Fix) extensions-builtin/sd_forge_dynamic_thresholding/lib_dynamic_thresholding/dynthres_core.py:61-125
  */
@@ -344,7 +347,7 @@ int fmx_embed_tokens(const int32_t* ids, const void* tok_emb, const void* pos_em
  * Sampler-side fused elementwise (fp32 latents NCHW [b][c][h][w], as the reference keeps them)
  * ---------------------------------------------------------------------------------------------- */
 /* UNet input pack: xc = x / sqrt(sigma^2 + sigma_data^2) (k_prediction.py:74-79) for `reps` stacked copies
- * of the batch (reps = 2 under CFG: [uncond ; cond]), written as the 3x3 im2col matrix of the first conv:
+ * of the batch (reps = 2 under CFG: [uncond ; cond]; 3 with the perturbed group of Perturbed-Attention Guidance; 1 <= reps <= 3), written as the 3x3 im2col matrix of the first conv:
  * out fp16 [reps*b*h*w][64], column (ky*3+kx)*c + ch for c*9 <= 64, zero elsewhere (zero padding taps). */
 int fmx_unet_pack_input(const float* x, const float* sigma, float sigma_data, int32_t b, int32_t c, int32_t h,
                         int32_t w, int32_t reps, void* out, void* stream);
@@ -687,6 +690,33 @@ int fmx_dynthresh_f32(const float* cond, const float* uncond, int32_t b, int32_t
  * ---------------------------------------------------------------------------------------------- */
 int fmx_resize_nhwc_f16(const void* in, void* out, const int32_t* ystart, const float* yweights, const int32_t* xstart, const float* xweights,
                         int32_t n, int32_t h, int32_t w, int32_t c, int32_t oh, int32_t ow, int32_t ky, int32_t kx, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Perturbed-Attention Guidance ("PerturbedAttentionGuidance Integrated", forge_perturbed_attention.py:62-83): a third group of rows
+ * [uncond ; cond ; perturbed] in one UNet batch.  In the middle block's self-attention the perturbed images' attention output is V
+ * (patches_replace attn1 ("middle", 0) = lambda q, k, v, to: v), and the guidance term joins calculate_denoised + the CFG combination.
+ * New symbols only: no existing signature moves, the ABI number stays 12.
+ *
+ * fmx_attn_value_rows_f16: the attention output of the images b0 .. b0 + nb - 1 is their V, which the executor holds feature-major:
+ *   out[b * o_bs + t * o_rs + f] = vt[f * vt_ds + b * vt_bs + t]      b0 <= b < b0 + nb, t < n, f < hd
+ *   vt : fmx_attention_f16's V^T operand with vt_hs = dpad * vt_ds, so that f = head * dpad + d (hd = heads * dpad); out : its O.
+ * A copy of 16-bit words, bit for bit; nothing outside those n x hd elements per image is written (rows n .. vt_bs - 1 of the ragged layout are
+ * neither copied nor touched in out).  A 64 token x 64 feature tile per workgroup through LDS (pitch padded: no bank conflict on either side),
+ * 16-byte loads along the tokens and 16-byte stores along the features; when a base pointer is not 16-byte aligned or vt_bs, vt_ds, o_rs or o_bs
+ * is not a multiple of 8 elements, the same tile with 2-byte accesses.  Token and feature tails are masked in the kernel.
+ * Requirements (FMX_E_BADARG otherwise, before any launch): pointers non-null; hd > 0, hd % 8 == 0; n > 0; b0 >= 0; 1 <= nb <= 65535;
+ * vt_bs >= n, vt_ds >= n, o_rs >= hd.
+ *
+ * fmx_cfg_pag_combine: fmx_cfg_combine with the perturbed group.  eps fp16 NHWC [(2 + has_uncond) * b][h][w][ld_eps]: [uncond ; cond ; perturbed]
+ * (has_uncond 1) or [cond ; perturbed] (0).  du, dc, dp = calculate_denoised of the groups, the expressions of fmx_cfg_combine;
+ *   den = du + (dc - du) * cond_scale   (has_uncond 0: 0 + (dc - 0) * cond_scale);      denoised = den + (dc - dp) * pag_scale
+ * cond_pred / uncond_pred (optional) carry the bits fmx_cfg_combine writes from the same rows; degraded_pred (optional) = dp.
+ * ---------------------------------------------------------------------------------------------- */
+int fmx_attn_value_rows_f16(const void* vt, int64_t vt_bs, int64_t vt_ds, void* out, int64_t o_rs, int64_t o_bs, int32_t hd, int32_t n,
+                            int32_t b0, int32_t nb, void* stream);
+int fmx_cfg_pag_combine(const void* eps, int32_t ld_eps, const float* x, const float* sigma, int32_t b, int32_t c, int32_t h, int32_t w,
+                        int32_t has_uncond, float cond_scale, float pag_scale, float* denoised, float* cond_pred, float* uncond_pred,
+                        float* degraded_pred, int32_t prediction_type, float sigma_data, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * HIP-graph helpers: capture everything launched on `stream` between begin/end into an executable graph.

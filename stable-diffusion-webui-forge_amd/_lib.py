@@ -182,6 +182,10 @@ SIGNATURES["fmx_dynthresh_f32"] = [_vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32,
 # NHWC fp16 resize of native Kohya HRFix (in, out, ystart, yweights, xstart, xweights, n, h, w, c, oh, ow, ky, kx, stream): a new symbol, the ABI
 # number does not move
 SIGNATURES["fmx_resize_nhwc_f16"] = [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]
+# native Perturbed-Attention Guidance: (vt, vt_bs, vt_ds, out, o_rs, o_bs, hd, n, b0, nb, stream) and fmx_cfg_combine's arguments with has_uncond
+# for reps, pag_scale after cond_scale and degraded_pred after uncond_pred: new symbols, the ABI number does not move
+SIGNATURES["fmx_attn_value_rows_f16"] = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp]
+SIGNATURES["fmx_cfg_pag_combine"] = [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _i32, _f32, _vp]
 
 
 def source_tree_hash():

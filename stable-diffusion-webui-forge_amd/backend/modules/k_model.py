@@ -88,14 +88,25 @@ class KModel:
         return entries
 
     def _forward_static(self, key, x, sigma_dev, sig_host, reps, ctxc, control=None, transformer_options=None, c_concat=None, control_plan=None,
-                        freeu=None, shrink=None):
+                        freeu=None, shrink=None, pag_from=None):
         """pack -> [ControlNets ->] UNet -> (returns eps view); static buffers per shape so the chain can be graph-replayed.
+        `reps`: the stacked copies of the batch: 1, 2 ([uncond ; cond]) or, with the perturbed group of native Perturbed-Attention Guidance
+        behind them, 2 or 3; `pag_from`: the first image of that group (backend/nn/unet.py), or None.  Such a call arrives with ("pag",) in `key`,
+        so its static buffers and its graph are its own: the steps inside and outside the PAG window of one job are two graphs.
         `freeu`: the job's native FreeU parameters (transformer_options["freeu_v2"], backend/patcher/freeu.py) or None.  They are launch
         arguments of the captured kernels, so they are part of the graph key: the steps inside and outside the FreeU window of one job
         are two graphs.
         `shrink`: the job's native Kohya HRFix parameters (transformer_options["kohya_hrfix"], backend/patcher/kohya_hrfix.py) when this step's
         host sigma lies inside their window, else None.  A shrunk forward launches other kernels on other shapes, so it is part of the graph
         key as well; a step outside the window replays the plain graph."""
+        if pag_from is not None:     # refused before any launch
+            if shrink is not None:
+                raise NotImplementedError("Perturbed-Attention Guidance and Kohya HRFix on the same step: the degraded pass of the reference runs "
+                                          "through the shrink patches as well; that combination has no native route")
+            if control is not None or control_plan:
+                raise NotImplementedError("Perturbed-Attention Guidance with a ControlNet / T2I-Adapter chain: the chain has no third group of rows")
+            if self.diffusion_model._hooks(transformer_options) is not None:
+                raise NotImplementedError("Perturbed-Attention Guidance (native) together with Python block hooks in transformer_options")
         if shrink is not None:
             if freeu is not None:
                 raise NotImplementedError("Kohya HRFix and native FreeU on one job: FreeU needs h and the skip at one size, and the two do not commute")
@@ -124,7 +135,8 @@ class KModel:
         concat_term = net.prepare_concat(c_concat, bu) if c_concat is not None else None  # cached per c_concat tensor: once per job
         if not self.use_graph or control is not None or hooks is not None:
             # Python hooks cannot be captured, and a ControlNet chain that needs Python per step arrives here with its residuals: eager
-            return net.forward_packed(st["xcol"], st["t"], ctxc, bu, hh, ww, control, hooks, concat_term, freeu=freeu, shrink=shrink)
+            return net.forward_packed(st["xcol"], st["t"], ctxc, bu, hh, ww, control, hooks, concat_term, freeu=freeu, shrink=shrink,
+                                      pag_from=pag_from)
         active = [e for e in control_plan if e["active"]] if control_plan else []
         gkey = key if not active else key + ("control",) + tuple(e["cm"].exec_serial for e in active)
         if freeu is not None:
@@ -140,7 +152,8 @@ class KModel:
             for e in reversed(active):
                 outs = e["cm"].forward_static(st["xcol"], st["t"], e["ctxc"], bu, hh, ww, e["gh"])
                 ctrl = e["cn"].control_merge(None, outs, ctrl, torch.float32)
-            return net.forward_packed(st["xcol"], st["t"], ctxc, bu, hh, ww, control=ctrl, concat_term=concat_term, freeu=freeu, shrink=shrink)
+            return net.forward_packed(st["xcol"], st["t"], ctxc, bu, hh, ww, control=ctrl, concat_term=concat_term, freeu=freeu, shrink=shrink,
+                                      pag_from=pag_from)
 
         def validity():
             # What a captured graph points at: the executors' arenas (re-allocated when a larger shape comes through, e.g. the hires pass),
@@ -192,11 +205,23 @@ class KModel:
         cur.wait_stream(s)
         return gs["eps"]
 
+    def has_middle_attention(self):
+        """whether Perturbed-Attention Guidance has anything to perturb: a model whose middle block holds no transformer gets no third group"""
+        from ..nn.layout import SpatialT
+        return any(isinstance(L, SpatialT) for L in self.diffusion_model.layout.middle)
+
     def denoise_cfg(self, x, sigma, uncond_ctx, cond_ctx, cond_scale, want_parts=False, transformer_options=None, control_model=None,
-                    c_concat=None):
+                    c_concat=None, pag_scale=None):
         """Fused path: returns CFG-combined denoised (fp32 NCHW) [+ cond_pred, uncond_pred].
         `uncond_ctx`/`cond_ctx`: (context [B,T,Dc], y or None); uncond_ctx None => cond_scale == 1 shortcut.
-        `transformer_options` with Python hooks: completed with the per-call keys of sampling_function.py:253-257 and run eagerly."""
+        `transformer_options` with Python hooks: completed with the per-call keys of sampling_function.py:253-257 and run eagerly.
+        `pag_scale`: None, or the step's scale of native Perturbed-Attention Guidance (backend/patcher/pag.py): the batch is
+        [uncond ; cond ; cond], the last group perturbed in the middle block, and (cond_pred - degraded_pred) * pag_scale joins the result in the
+        combine kernel; with want_parts the degraded prediction is returned as a fourth value (None for a model without middle attention,
+        where the term is exactly zero and nothing is added to the batch)."""
+        if pag_scale is not None:
+            return self._denoise_cfg_pag(x, sigma, uncond_ctx, cond_ctx, cond_scale, want_parts, transformer_options, control_model, c_concat,
+                                         float(pag_scale))
         b, c, hh, ww = x.shape
         reps = 1 if uncond_ctx is None else 2
         job_options = transformer_options
@@ -242,6 +267,54 @@ class KModel:
         den = ops.cfg_combine(eps, eps.shape[-1], x, sigma, reps, cond_scale, None, cond_pred, uncond_pred,
                               prediction_type=self.predictor.prediction_type, sigma_data=self.predictor.sigma_data)
         return (den, cond_pred, uncond_pred) if want_parts else den
+
+    def _denoise_cfg_pag(self, x, sigma, uncond_ctx, cond_ctx, cond_scale, want_parts, transformer_options, control_model, c_concat, pag_scale):
+        """denoise_cfg on a step that applies Perturbed-Attention Guidance.  Everything it cannot carry is refused before any launch."""
+        if control_model is not None:
+            raise NotImplementedError("Perturbed-Attention Guidance with a ControlNet / T2I-Adapter chain: the chain has no third group of rows")
+        if self.diffusion_model._hooks(transformer_options) is not None:
+            raise NotImplementedError("Perturbed-Attention Guidance (native) together with Python block hooks in transformer_options")
+        sig_host = host_sigmas(sigma)
+        shrink = shrink_for_step(transformer_options, sig_host)
+        if shrink is not None:
+            raise NotImplementedError("Perturbed-Attention Guidance and Kohya HRFix on the same step: the degraded pass of the reference runs "
+                                      "through the shrink patches as well; that combination has no native route")
+        if not self.has_middle_attention():
+            out = self.denoise_cfg(x, sigma, uncond_ctx, cond_ctx, cond_scale, want_parts, transformer_options, None, c_concat)
+            return out + (None,) if want_parts else out
+        b, c, hh, ww = x.shape
+        has_uncond = uncond_ctx is not None
+        groups = 3 if has_uncond else 2
+        ctx = self._stack_ctx_pag(uncond_ctx, cond_ctx)
+        ctxc = self.diffusion_model.prepare_context(ctx[0], ctx[1])
+        key = (b, c, hh, ww, groups - 1, "pag")
+        eps = self._forward_static(key, x, sigma, sig_host, groups, ctxc, c_concat=c_concat, freeu=(transformer_options or {}).get("freeu_v2"),
+                                   pag_from=(groups - 1) * b)
+        cond_pred = torch.empty_like(x) if want_parts else None
+        uncond_pred = torch.empty_like(x) if want_parts else None
+        degraded = torch.empty_like(x) if want_parts else None
+        den = ops.cfg_pag_combine(eps, eps.shape[-1], x, sigma, has_uncond, cond_scale, pag_scale, None, cond_pred, uncond_pred, degraded,
+                                  prediction_type=self.predictor.prediction_type, sigma_data=self.predictor.sigma_data)
+        return (den, cond_pred, uncond_pred, degraded) if want_parts else den
+
+    def _stack_ctx_pag(self, uc, c):
+        """[uncond ; cond ; cond] (or [cond ; cond]) along batch: the perturbed group carries the cond group's context and y.  Cached like
+        _stack_ctx, on the identity of the parts."""
+        parts = ([uc] if uc is not None else []) + [c]
+        key = tuple((p[0].data_ptr(), tensor_version(p[0]), tuple(p[0].shape), None if p[1] is None else p[1].data_ptr()) for p in parts)
+        cached = getattr(self, "_stacked_pag", None)
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        if uc is not None:
+            ctx, y = self._stack_ctx(uc, c)
+            b = c[0].shape[0]
+            ctx = torch.cat([ctx, ctx[b:]]).contiguous()
+            y = None if y is None else torch.cat([y, y[b:]]).contiguous()
+        else:
+            ctx = torch.cat([c[0], c[0]]).contiguous()
+            y = None if c[1] is None else torch.cat([c[1], c[1]]).contiguous()
+        self._stacked_pag = (key, (ctx, y), parts)
+        return ctx, y
 
     def _stack_ctx(self, uc, c):
         """[uncond ; cond] along batch (sampling_function.py:187-236 order); cached on the identity of the parts."""

@@ -373,10 +373,26 @@ class IntegratedUNet2DConditionModel:
         arena.release(m)
         return ops.attach_stats(out, st)
 
-    def _attn_block(self, b, L, h, bu, n, ctxc, arena, rs1=None, want_next=False):
+    def _self_attention(self, qk, vt, bu, n, npad, H, d, pag_from):
+        """O [Bu * n, H * dp] of attn1 from [Q | K] rows and V^T, `npad` rows / columns per image in both (= n unless the token count is ragged).
+        pag_from: None, or the first image of the perturbed group of native Perturbed-Attention Guidance -- the images from there on get O = V
+        (the reference's attn1 replace patch `lambda q, k, v, to: v`), one transposing copy out of V^T, and no attention."""
+        dp = _dpad(d)
+        hd = H * dp
+        m_pad = bu * npad
+        kw = dict(heads=H, nq=n, nk=n, nk_pad=npad, dpad=dp, scale=d ** -0.5, q_bs=npad * 2 * hd, q_rs=2 * hd, k_bs=npad * 2 * hd, k_rs=2 * hd,
+                  vt_bs=npad, vt_hs=dp * m_pad, vt_ds=m_pad)
+        if pag_from is None:
+            return ops.attention(qk, qk[:, hd:], vt, batch=bu, **kw)
+        o = ops.empty((bu * n, hd))
+        ops.attention(qk, qk[:, hd:], vt, batch=pag_from, out=o, **kw)
+        return ops.attn_value_rows(vt, o, first=pag_from, count=bu - pag_from, n=n, hd=hd, vt_bs=npad, vt_ds=m_pad)
+
+    def _attn_block(self, b, L, h, bu, n, ctxc, arena, rs1=None, want_next=False, pag_from=None):
         """One BasicTransformerBlock on h [M, C] (updated in place).  rs1: the row statistics the projection that WROTE h left (proj_in or the
         previous block's ff.net.2) -- norm1 then runs folded into the q|k and V^T projections; want_next: leave the statistics of this block's
-        output for the next block's norm1.  -> that RowStats (or None)."""
+        output for the next block's norm1.  pag_from: see _self_attention (everything but the attention itself runs on all rows).
+        -> that RowStats (or None)."""
         H, d = L.heads, L.dim_head
         dp = _dpad(d)
         hd = H * dp
@@ -396,15 +412,13 @@ class IntegratedUNet2DConditionModel:
             wvf, vcb = self.w[b + ".attn1.v.ln"]
             vt = ops.conv_gemm(wvf, h, m_tok, ln_swapped=(ab, vcb))                                   # [H*dp, M] = V^T of LN(h)
             self._tap_qkv(b + ".attn1", qk[:, :hd].view(bu, n, hd), qk[:, hd:].view(bu, n, hd), vt.view(hd, bu, n))
-            o = ops.attention(qk, qk[:, hd:], vt, batch=bu, heads=H, nq=n, nk=n, nk_pad=n, dpad=dp, scale=d ** -0.5,
-                              q_bs=n * 2 * hd, q_rs=2 * hd, k_bs=n * 2 * hd, k_rs=2 * hd, vt_bs=n, vt_hs=dp * m_tok, vt_ds=m_tok)
+            o = self._self_attention(qk, vt, bu, n, n, H, d, pag_from)
         elif n % 64 == 0:
             n1 = ops.layernorm(h, *self.w[b + ".norm1"])
             qk = ops.linear(n1, self.w[b + ".attn1.qk"])                   # [M, 2*H*dp] = [Q | K]
             vt = ops.conv_gemm(self.w[b + ".attn1.v"], n1, m_tok)          # [H*dp, M] = V^T (operand swap)
             self._tap_qkv(b + ".attn1", qk[:, :hd].view(bu, n, hd), qk[:, hd:].view(bu, n, hd), vt.view(hd, bu, n))
-            o = ops.attention(qk, qk[:, hd:], vt, batch=bu, heads=H, nq=n, nk=n, nk_pad=n, dpad=dp, scale=d ** -0.5,
-                              q_bs=n * 2 * hd, q_rs=2 * hd, k_bs=n * 2 * hd, k_rs=2 * hd, vt_bs=n, vt_hs=dp * m_tok, vt_ds=m_tok)
+            o = self._self_attention(qk, vt, bu, n, n, H, d, pag_from)
         else:
             # ragged token count (latent H*W not a multiple of the 64-key tile, e.g. SDXL at 832x1216): LayerNorm writes each image's tokens
             # at a padded stride into a persistent zero-filled buffer, so Q|K and V^T are still ONE batched GEMM each over [Bu * n_pad]
@@ -422,9 +436,10 @@ class IntegratedUNet2DConditionModel:
             p2d = padbuf.view(bu * npad, -1)
             qk = ops.linear(p2d, self.w[b + ".attn1.qk"])                  # [Bu*n_pad, 2*H*dp]
             vt = ops.conv_gemm(self.w[b + ".attn1.v"], p2d, bu * npad)     # [H*dp, Bu*n_pad]
-            o = ops.attention(qk, qk[:, hd:], vt, batch=bu, heads=H, nq=n, nk=n, nk_pad=npad, dpad=dp, scale=d ** -0.5,
-                              q_bs=npad * 2 * hd, q_rs=2 * hd, k_bs=npad * 2 * hd, k_rs=2 * hd, vt_bs=npad,
-                              vt_hs=dp * bu * npad, vt_ds=bu * npad)
+            if pag_from is not None:
+                self._tap_qkv(b + ".attn1", qk[:, :hd].view(bu, npad, hd)[:, :n], qk[:, hd:].view(bu, npad, hd)[:, :n],
+                              vt.view(hd, bu, npad)[:, :, :n])
+            o = self._self_attention(qk, vt, bu, n, npad, H, d, pag_from)
         self._tap(b + ".attn1.o", o.view(bu, n, -1))
         ops.linear(o, *self.w[b + ".attn1.out"], residual=h, out=h, ld_out=h.shape[1], row_stats=rs2)
         arena.release(mk)
@@ -564,7 +579,7 @@ class IntegratedUNet2DConditionModel:
             return h
         return r.permute(0, 2, 3, 1).to(torch.float16).contiguous()
 
-    def _spatial_transformer(self, L, x, ctxc, arena, to=None):
+    def _spatial_transformer(self, L, x, ctxc, arena, to=None, pag_from=None):
         k = L.key
         bu, hh, ww, c = x.shape
         n = hh * ww
@@ -574,6 +589,8 @@ class IntegratedUNet2DConditionModel:
         mk = arena.mark()
         g = ops.groupnorm(x, *self.w[k + ".norm"], 1e-6)
         hooked = to is not None and (to.get("patches") or to.get("patches_replace"))
+        if hooked and pag_from is not None:
+            raise NotImplementedError("Perturbed-Attention Guidance (native) together with Python transformer patches")
         # norm1 of every block folded into its q|k / V^T projections: the GEMM that writes h (proj_in, then each block's ff.net.2) leaves the row sums
         fold1 = _LN_FOLD and _LN_FOLD1 and not hooked and n % 64 == 0 and (f"{k}.transformer_blocks.0.attn1.v.ln") in self.w
         rs1 = ops.RowStats(bu * n, inner) if fold1 else None
@@ -584,7 +601,8 @@ class IntegratedUNet2DConditionModel:
                 to["block_index"] = di
                 self._attn_block_hooked(f"{k}.transformer_blocks.{di}", L, h, bu, n, ctxc, arena, to)
             else:
-                rs1 = self._attn_block(f"{k}.transformer_blocks.{di}", L, h, bu, n, ctxc, arena, rs1=rs1, want_next=fold1 and di + 1 < L.depth)
+                rs1 = self._attn_block(f"{k}.transformer_blocks.{di}", L, h, bu, n, ctxc, arena, rs1=rs1, want_next=fold1 and di + 1 < L.depth,
+                                       pag_from=pag_from)
             self._tap(f"{k}.transformer_blocks.{di}", h.view(bu, n, -1))
         _, st = ops.linear(h, *self.w[k + ".proj_out"], residual=x.view(-1, c), out=out.view(-1, c), ld_out=c, n=bu, h=hh, w=ww, stats=True,
                            stats_partial=out_part)
@@ -613,7 +631,7 @@ class IntegratedUNet2DConditionModel:
             return Upsample(key=L.key)
         return Conv2d(key=L.key)
 
-    def _run_block(self, blk, h, skip, emb_all, ctxc, arena, up_to=None, to=None):
+    def _run_block(self, blk, h, skip, emb_all, ctxc, arena, up_to=None, to=None, pag_from=None):
         inner = to.get("block_inner_modifiers", []) if to is not None else []
         wrapper = to.get("group_norm_wrapper") if to is not None else None
         standins = TimestepEmbedSequential(self._layer_standin(L) for L in blk) if inner else None
@@ -635,7 +653,7 @@ class IntegratedUNet2DConditionModel:
                 h = self._res(L, h, skip, emb_all, arena)
                 skip = None
             elif isinstance(L, SpatialT):
-                h = self._spatial_transformer(L, h, ctxc, arena, to)
+                h = self._spatial_transformer(L, h, ctxc, arena, to, pag_from)
                 if to is not None and "transformer_index" in to:
                     to["transformer_index"] += 1  # unet.py:82-84
             elif isinstance(L, Down):
@@ -708,7 +726,7 @@ class IntegratedUNet2DConditionModel:
         self._concat_cache = (key, term, c_concat)
         return term
 
-    def _forward_impl(self, xcol, t, ctxc, bu, hh, ww, arena, control=None, to=None, concat_term=None, freeu=None, shrink=None):
+    def _forward_impl(self, xcol, t, ctxc, bu, hh, ww, arena, control=None, to=None, concat_term=None, freeu=None, shrink=None, pag_from=None):
         """xcol: [Bu*H*W, 64] im2col of the (scaled) input; t: [Bu] fp32 table indices.  -> eps [Bu*H*W, out_ch].
         `to`: transformer_options with Python hooks (unet.py:696-763 hook points), or None on the fast path.
         `freeu`: a FreeUParams tuple (b1, b2, s1, s2, ...) of backend/patcher/freeu.py, or None: native FreeU v2 on the inputs of the
@@ -719,7 +737,20 @@ class IntegratedUNet2DConditionModel:
         `block_number` h is resized to round(extent / factor) -- after the skip is stored, or before it (downscale_after_skip False) -- and at every
         output block whose popped skip has another height h is resized to the skip's size, where the reference's input_block_patch(_after_skip)
         and output_block_patch run (kohya_hrfix.py:13-28).  Not a Python hook either: fast path, captured graph; Python patches of the same
-        job run after it.  The caller decides the sigma window (KModel hands the option over only inside it)."""
+        job run after it.  The caller decides the sigma window (KModel hands the option over only inside it).
+        `pag_from`: None, or the first image of the perturbed group of native Perturbed-Attention Guidance (backend/patcher/pag.py; KModel stacks
+        [uncond ; cond ; cond] and hands over 2b, or b without uncond).  The images from there on get V as the self-attention output of EVERY
+        transformer block of the middle block -- the reference's patches_replace key ("middle", 0) carries no block index, so it matches all of
+        them (attention.py / unet.py:201-214) -- and run like the others everywhere else.  Fast path, captured graph."""
+        if pag_from is not None:
+            if not 0 < pag_from < bu:
+                raise ValueError(f"pag_from {pag_from} outside the batch of {bu}")
+            if to is not None:
+                raise NotImplementedError("Perturbed-Attention Guidance (native) together with Python block hooks in transformer_options")
+            if shrink is not None:
+                raise NotImplementedError("Perturbed-Attention Guidance and Kohya HRFix on the same step")
+            if control is not None and any(len(v) > 0 for v in control.values()):
+                raise NotImplementedError("Perturbed-Attention Guidance with ControlNet / T2I-Adapter residuals: the chain has no third group of rows")
         if shrink is not None:
             if freeu is not None:
                 raise NotImplementedError("Kohya HRFix and native FreeU on one job: FreeU needs h and the skip at one size, and the two do not commute")
@@ -794,7 +825,7 @@ class IntegratedUNet2DConditionModel:
         if to is not None:
             to["block"] = ("middle", 0)
         h = modify(h, "before")
-        h = self._run_block(lay.middle, h, None, emb_all, ctxc, arena, to=to)
+        h = self._run_block(lay.middle, h, None, emb_all, ctxc, arena, to=to, pag_from=pag_from)
         h = self._apply_control(h, control, "middle")
         h = modify(h, "after")
         for bi, blk in enumerate(lay.output_blocks):
@@ -869,17 +900,18 @@ class IntegratedUNet2DConditionModel:
             self.arena_epoch += 1
         return self._arena
 
-    def forward_packed(self, xcol, t, ctxc, bu, hh, ww, control=None, transformer_options=None, concat_term=None, freeu=None, shrink=None):
+    def forward_packed(self, xcol, t, ctxc, bu, hh, ww, control=None, transformer_options=None, concat_term=None, freeu=None, shrink=None,
+                       pag_from=None):
         """Hot-path entry (no layout conversion): returns eps as fp16 [Bu*H*W, out_channels] living in the arena
         (valid until the next forward).  `freeu`, `shrink`: see _forward_impl (the caller takes them out of transformer_options["freeu_v2"] /
-        ["kohya_hrfix"])."""
+        ["kohya_hrfix"]); `pag_from`: see _forward_impl."""
         while True:
             arena = self._get_arena(bu, hh, ww)
             arena.reset()
             try:
                 with arena:
                     return self._forward_impl(xcol, t, ctxc, bu, hh, ww, arena, control, self._hooks(transformer_options), concat_term, freeu,
-                                              shrink)
+                                              shrink, pag_from)
             except ArenaOverflow:
                 torch.cuda.synchronize(self.device)
                 self._arena_bytes = arena.capacity * 2

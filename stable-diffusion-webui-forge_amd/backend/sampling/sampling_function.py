@@ -221,10 +221,36 @@ def calc_cond_uncond_batch(model, cond, uncond, x_in, timestep, model_options, c
     return None, cond_pred, uncond_pred
 
 
+def _pag_cond_uncond_batch(model, cond, uncond, x_in, timestep, model_options, cond_scale, pag):
+    """A step that applies native Perturbed-Attention Guidance (model_options["pag"], backend/patcher/pag.py): the fused route with a third group
+    of rows -> (cfg result with the guidance term, cond_pred, uncond_pred, degraded_pred or None).  The third group exists on that route only, so
+    everything that would leave it is refused, before any launch."""
+    from ..patcher.pag import FEATURE
+    _check_supported(cond, "cond")
+    if uncond is not None:
+        _check_supported(uncond, "uncond")
+    if not hasattr(model, "has_middle_attention"):
+        raise NotImplementedError(f"{FEATURE}: UNet models only")          # Flux: the reference's key ("middle", 0) matches nothing there
+    if _is_regional(cond) or _is_regional(uncond):
+        raise NotImplementedError(f"{FEATURE} with regional or time-ranged conditioning: not on the fused route")
+    if "model_function_wrapper" in model_options:
+        raise NotImplementedError(f"{FEATURE} with a model_function_wrapper: not on the fused route")
+    if not _fused_ok(model, cond, uncond, model_options):
+        raise NotImplementedError(f"{FEATURE} with AND-composed or weighted conditionings: not on the fused route")
+    cctx = _single(cond, "cond")
+    uctx = _single(uncond, "uncond") if uncond is not None else None
+    cc = cond[0]["model_conds"].get("c_concat")
+    return model.denoise_cfg(x_in, timestep, uctx, cctx, cond_scale, want_parts=True, transformer_options=model_options.get("transformer_options"),
+                             control_model=cond[0].get("control"), pag_scale=pag.scale, **({"c_concat": cc.cond} if cc is not None else {}))
+
+
 def sampling_function_inner(model, x, timestep, uncond, cond, cond_scale, model_options={}, seed=None, return_full=False):
     """:292-322, including the sampler_pre_cfg / sampler_cfg / sampler_post_cfg function hooks and the edit-strength form of the CFG
     formula for AND-composed prompts.  model_options["dynthresh"] (without a Python sampler_cfg_function) is the native form of the Dynamic
-    Thresholding script's CFG function: it does not move the step off the fused route."""
+    Thresholding script's CFG function: it does not move the step off the fused route.  model_options["pag"] with a positive current scale is
+    native Perturbed-Attention Guidance: the step runs a third group of rows in the same UNet call and the guidance term joins the fused
+    combination (or, when a CFG function replaces that combination, is added to its result), before any Python sampler_post_cfg_function; the
+    scale then drops by its attenuation, once per model call."""
     from ... import hipops as ops
     edit_strength = sum((item["strength"] if "strength" in item else 1) for item in cond)
     if math.isclose(cond_scale, 1.0) and not model_options.get("disable_cfg1_optimization", False):
@@ -235,7 +261,13 @@ def sampling_function_inner(model, x, timestep, uncond, cond, cond_scale, model_
         model, cond, uncond_, x, timestep, model_options = fn(model, cond, uncond_, x, timestep, model_options)
     custom_cfg = "sampler_cfg_function" in model_options
     fused_scale = None if (custom_cfg or not math.isclose(edit_strength, 1.0)) else cond_scale
-    cfg_result, cond_pred, uncond_pred = calc_cond_uncond_batch(model, cond, uncond_, x, timestep, model_options, fused_scale)
+    from ..patcher.pag import pag_for_call
+    pag, degraded_pred = pag_for_call(model_options), None
+    if pag is not None:
+        pag_scale = pag.scale
+        cfg_result, cond_pred, uncond_pred, degraded_pred = _pag_cond_uncond_batch(model, cond, uncond_, x, timestep, model_options, cond_scale, pag)
+    else:
+        cfg_result, cond_pred, uncond_pred = calc_cond_uncond_batch(model, cond, uncond_, x, timestep, model_options, fused_scale)
     if custom_cfg:
         args = {"cond": x - cond_pred, "uncond": x - uncond_pred, "cond_scale": cond_scale, "timestep": timestep, "input": x, "sigma": timestep,
                 "cond_denoised": cond_pred, "uncond_denoised": uncond_pred, "model": model, "model_options": model_options}
@@ -254,6 +286,11 @@ def sampling_function_inner(model, x, timestep, uncond, cond, cond_scale, model_
     elif cfg_result is None:
         k = cond_scale * edit_strength if not math.isclose(edit_strength, 1.0) else cond_scale
         cfg_result = ops.lincomb([uncond_pred.contiguous(), cond_pred.contiguous()], [1.0 - k, k])  # uncond + (cond - uncond) * k
+    if pag is not None:
+        if degraded_pred is not None and (custom_cfg or model_options.get("dynthresh") is not None):
+            # the fused combination, which carried the term, was discarded above: result + (cond_denoised - degraded) * scale
+            cfg_result = ops.lincomb([cfg_result.contiguous(), cond_pred, degraded_pred], [1.0, pag_scale, -pag_scale])
+        pag.applied()
     for fn in model_options.get("sampler_post_cfg_function", []):
         args = {"denoised": cfg_result, "cond": cond, "uncond": uncond, "model": model, "uncond_denoised": uncond_pred, "cond_denoised": cond_pred,
                 "sigma": timestep, "model_options": model_options, "input": x}
@@ -286,6 +323,10 @@ def sampling_function(self, denoiser_params, cond_scale, cond_composition):
         # native FreeU (backend/patcher/freeu.py): the reference's on_cfg_denoiser callback switches the patch off outside its step window
         from ..patcher.freeu import options_for_step
         model_options = options_for_step(model_options, denoiser_params.sampling_step, denoiser_params.total_sampling_steps)
+    if model_options.get("pag") is not None:
+        # native Perturbed-Attention Guidance (backend/patcher/pag.py): the reference's on_cfg_denoiser callback does the window test
+        from ..patcher.pag import options_for_step as pag_options_for_step
+        model_options = pag_options_for_step(model_options, denoiser_params.sampling_step, denoiser_params.total_sampling_steps)
     for modifier in model_options.get("conditioning_modifiers", []):  # :359-360
         model, x, timestep, uncond, cond, cond_scale, model_options, seed = modifier(model, x, timestep, uncond, cond, cond_scale, model_options, seed)
     return sampling_function_inner(model, x, timestep, uncond, cond, cond_scale, model_options, seed, return_full=True)
@@ -295,6 +336,8 @@ def sampling_prepare(unet, x):
     """:366-399: the VRAM juggling (load_models_gpu) has nothing to do here -- weights are resident; what remains is handing every
     ControlNet the predictor and its sigma range (:393-397)."""
     real_model = unet.model
+    from ..patcher.pag import reset as pag_reset
+    pag_reset(unet)     # Perturbed-Attention Guidance: every sampling pass starts at the full scale (process_before_every_sampling)
     for cnet in unet.list_controlnets():
         cnet.pre_run(real_model, lambda p: real_model.predictor.percent_to_sigma(p))
 

@@ -175,6 +175,55 @@ __global__ void cfg_combine_kernel(const f16* __restrict__ eps, int ld, const fl
   }
 }
 
+// cfg_combine_kernel with a third group of rows, the Perturbed-Attention Guidance pass: eps = [uncond ; cond ; perturbed] (has_uncond) or
+// [cond ; perturbed]; then  den + (dc - dp) * pag_scale  in the reference's order (forge_perturbed_attention.py:80).
+// cond_pred / uncond_pred must carry the bits cfg_combine_kernel writes from the same rows, so nothing here is left to the compiler's contraction:
+// it is switched off and every fused multiply-add is written out, in the forms cfg_combine_kernel compiles to (tests/test_gpu_pag.py compares the
+// bits on the device):  v = fma(s, s, sd^2);  epsilon: fma(-s, e, x) in both branches;  v_prediction / edm: fma(cb, e, round(x ca)) with two
+// halves, fma(ca, x, round(cb e)) with one;  den = fma(cond_scale, dc - du, du), with one half cond_scale * dc.
+__global__ void cfg_pag_combine_kernel(const f16* __restrict__ eps, int ld, const float* __restrict__ x, const float* __restrict__ sigma,
+                                       int b, int c, int h, int w, int has_uncond, float cond_scale, float pag_scale, float* __restrict__ den,
+                                       float* __restrict__ cond_pred, float* __restrict__ uncond_pred, float* __restrict__ degraded_pred,
+                                       int pred_type, float sigma_data) {
+#pragma clang fp contract(off)
+  const long total = (long)b * c * h * w;
+  const long hw = (long)h * w;
+  const int gc = has_uncond ? 1 : 0;   // the cond group's index; the perturbed group follows it
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long pix = i % hw;
+    const int ch = (int)((i / hw) % c);
+    const int bi = (int)(i / (hw * c));
+    const float s = sigma[bi];
+    float ca = 1.f, cb = -s;
+    if (pred_type != 0) {
+      const float sd2 = sigma_data * sigma_data;
+      const float v = fmaf(s, s, sd2);
+      ca = sd2 / v;
+      cb = ((pred_type == 1 ? -s : s) * sigma_data) / sqrtf(v);
+    }
+    const float xv = x[i];
+    const float ec = (float)eps[((long)(gc * b + bi) * hw + pix) * ld + ch];
+    const float ep = (float)eps[((long)((gc + 1) * b + bi) * hw + pix) * ld + ch];
+    float du = 0.f, dc, dp, result;
+    if (has_uncond) {
+      const float eu = (float)eps[((long)bi * hw + pix) * ld + ch];
+      const float ax = xv * ca;
+      du = pred_type == 0 ? fmaf(-s, eu, xv) : fmaf(cb, eu, ax);
+      dc = pred_type == 0 ? fmaf(-s, ec, xv) : fmaf(cb, ec, ax);
+      dp = pred_type == 0 ? fmaf(-s, ep, xv) : fmaf(cb, ep, ax);
+      result = fmaf(cond_scale, dc - du, du);
+    } else {
+      dc = pred_type == 0 ? fmaf(-s, ec, xv) : fmaf(ca, xv, cb * ec);
+      dp = pred_type == 0 ? fmaf(-s, ep, xv) : fmaf(ca, xv, cb * ep);
+      result = cond_scale * dc;
+    }
+    if (cond_pred) cond_pred[i] = dc;
+    if (uncond_pred) uncond_pred[i] = du;
+    if (degraded_pred) degraded_pred[i] = dp;
+    den[i] = fmaf(pag_scale, dc - dp, result);
+  }
+}
+
 __global__ void euler_step_kernel(const float* __restrict__ x, const float* __restrict__ den, float sigma, float sigma_next,
                                   const float* __restrict__ noise, float noise_scale, float* __restrict__ out, long n) {
   const float dt = sigma_next - sigma;
@@ -551,7 +600,7 @@ extern "C" int fmx_cast_f32_to_f16(const float* x, void* y, int64_t n, void* str
 
 extern "C" int fmx_unet_pack_input(const float* x, const float* sigma, float sigma_data, int32_t b, int32_t c, int32_t h, int32_t w,
                                    int32_t reps, void* out, void* stream) {
-  FMX_REQUIRE(x && sigma && out && b > 0 && c > 0 && c * 9 <= 64 && h > 0 && w > 0 && (reps == 1 || reps == 2), "unet_pack_input: bad args");
+  FMX_REQUIRE(x && sigma && out && b > 0 && c > 0 && c * 9 <= 64 && h > 0 && w > 0 && reps >= 1 && reps <= 3, "unet_pack_input: bad args");
   const long total = (long)reps * b * h * w * 9;
   hipLaunchKernelGGL(unet_pack_input_kernel, dim3(grid_for(total)), dim3(TPB), 0, (hipStream_t)stream, x, sigma, sigma_data * sigma_data,
                      b, c, h, w, reps, (f16*)out);
@@ -578,6 +627,19 @@ extern "C" int fmx_cfg_combine(const void* eps, int32_t ld_eps, const float* x, 
   hipLaunchKernelGGL(cfg_combine_kernel, dim3(grid_for(total)), dim3(TPB), 0, (hipStream_t)stream, (const f16*)eps, ld_eps, x, sigma, b, c,
                      h, w, reps, cond_scale, denoised, cond_pred, uncond_pred, prediction_type, sigma_data);
   FMX_LAUNCH_CHECK("fmx_cfg_combine");
+  return FMX_OK;
+}
+
+extern "C" int fmx_cfg_pag_combine(const void* eps, int32_t ld_eps, const float* x, const float* sigma, int32_t b, int32_t c, int32_t h,
+                                   int32_t w, int32_t has_uncond, float cond_scale, float pag_scale, float* denoised, float* cond_pred,
+                                   float* uncond_pred, float* degraded_pred, int32_t prediction_type, float sigma_data, void* stream) {
+  FMX_REQUIRE(eps && x && sigma && denoised && b > 0 && c > 0 && h > 0 && w > 0 && ld_eps >= c && (has_uncond == 0 || has_uncond == 1) &&
+                  prediction_type >= 0 && prediction_type <= 2 && sigma_data > 0.f,
+              "cfg_pag_combine: bad args");
+  const long total = (long)b * c * h * w;
+  hipLaunchKernelGGL(cfg_pag_combine_kernel, dim3(grid_for(total)), dim3(TPB), 0, (hipStream_t)stream, (const f16*)eps, ld_eps, x, sigma, b, c,
+                     h, w, has_uncond, cond_scale, pag_scale, denoised, cond_pred, uncond_pred, degraded_pred, prediction_type, sigma_data);
+  FMX_LAUNCH_CHECK("fmx_cfg_pag_combine");
   return FMX_OK;
 }
 

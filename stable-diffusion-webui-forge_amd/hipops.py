@@ -858,6 +858,31 @@ def cfg_combine(eps, ld_eps, x, sigma, reps, cond_scale, denoised=None, cond_pre
     return denoised
 
 
+def cfg_pag_combine(eps, ld_eps, x, sigma, has_uncond, cond_scale, pag_scale, denoised=None, cond_pred=None, uncond_pred=None,
+                    degraded_pred=None, prediction_type="epsilon", sigma_data=1.0):
+    """cfg_combine over [uncond ; cond ; perturbed] (has_uncond) or [cond ; perturbed] rows of eps, plus (cond - perturbed) * pag_scale: native
+    Perturbed-Attention Guidance (include/fmx.h, section "Perturbed-Attention Guidance").  degraded_pred: optional fp32 output, the perturbed
+    group's denoised."""
+    b, c, h, w = x.shape
+    if denoised is None:
+        denoised = torch.empty_like(x)
+    _lib.check(_lib.lib().fmx_cfg_pag_combine(_p(eps), ld_eps, _p(x), _p(sigma), b, c, h, w, 1 if has_uncond else 0, float(cond_scale),
+                                              float(pag_scale), _p(denoised), _p(cond_pred), _p(uncond_pred), _p(degraded_pred),
+                                              PREDICTION_TYPES[prediction_type], float(sigma_data), stream_ptr()), "fmx_cfg_pag_combine")
+    return denoised
+
+
+def attn_value_rows(vt, out, *, first, count, n, hd, vt_bs, vt_ds, o_bs=None):
+    """out[b, t, :hd] = V of image b, token t, for first <= b < first + count: the self-attention output of Perturbed-Attention Guidance's degraded
+    images.  vt / out / the strides are ops.attention's V^T operand and O (out: [rows, >= hd] view, stride(0) the row stride; o_bs defaults to
+    n * out.stride(0))."""
+    _check_f16(vt, out)
+    _lib.check(_lib.lib().fmx_attn_value_rows_f16(_p(vt), int(vt_bs), int(vt_ds), _p(out), out.stride(0),
+                                                  n * out.stride(0) if o_bs is None else int(o_bs), hd, n, first, count, stream_ptr()),
+               "fmx_attn_value_rows_f16")
+    return out
+
+
 def euler_step(x, denoised, sigma, sigma_next, noise=None, noise_scale=0.0, out=None):
     if out is None:
         out = torch.empty_like(x)

@@ -9,6 +9,9 @@ batch sizes -- and what they cost.
                                                      sampler_cfg_function, interleaved in one process, device events around every job
     python tools/bench_features.py --only kohya      Kohya HRFix: plain / native (transformer option, captured graph) / the same arithmetic as the
                                                      reference's Python patches (eager), interleaved in one process, device events around every job
+    python tools/bench_features.py --only pag        Perturbed-Attention Guidance: plain / native (third group of rows in the captured graph) / the same
+                                                     arithmetic as a Python post-CFG function with an attn1 replace patch (a second, eager model call),
+                                                     interleaved in one process, device events around every job
     python tools/bench_features.py --only taesd      the TAESD decode of batch x (res/8)^2 SDXL-shaped latents (synthetic weights, fp16) next to the Full
                                                      VAE decode of the same latents in the same process: median of 5 after warm-up, events around the calls
 """
@@ -73,6 +76,7 @@ def main():
     ap.add_argument("--width", type=int, default=0)
     ap.add_argument("--height", type=int, default=0)
     ap.add_argument("--only", default="samplers,controlnet,hooks,freeu,and,hires")
+    ap.add_argument("--pag-routes", default="plain,pag_native,pag_python", help="the routes of --only pag (one route alone for a kernel trace of it)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     width, height = a.width or a.res, a.height or a.res
@@ -322,8 +326,92 @@ def main():
                           "resize_calls_per_unet_call": [[list(s[0]), list(s[1]), s[2]] for s in per_call],
                           "resize_kernels_ms_per_unet_call": round(sorted(kern)[len(kern) // 2], 4), "finite": finite, "shape": list(lat.shape)}), flush=True)
 
+    def pag_leg(rounds=5, scale=3.0):
+        """Plain, native Perturbed-Attention Guidance (model option, a third group of rows in the captured graph) and the same arithmetic as the
+        reference script installs it (tests/pag_refs.py: a post-CFG function that calls the model again with an attn1 replace patch, on the eager
+        hooked executor), no attenuation and the window open, so that every timed step is a guided one -- primed once each, then timed
+        alternately, `rounds` jobs of a.steps steps per variant in this one process, device events around each job.  Also the copy kernel of one
+        UNet call's middle block on its own next to a plain device copy of the same bytes (events, median of 20)."""
+        import pag_refs as pr_
+        from forge_amd import hipops as ops
+        from forge_amd.backend.patcher.pag import patch_pag
+        variants = {"plain": None, "pag_native": patch_pag(eng.forge_objects.unet, scale), "pag_python": pr_.python_pag(eng.forge_objects.unet, scale)}
+        variants = {k: v for k, v in variants.items() if k in a.pag_routes.split(",")}
+        calls = []                        # (V^T shape, out shape, window, n, hd) of every ops.attn_value_rows call
+        real = ops.attn_value_rows
+        ops.attn_value_rows = lambda vt, out, **kw: (calls.append((tuple(vt.shape), tuple(out.shape), kw)), real(vt, out, **kw))[1]
+        saved = eng.forge_objects_after_applying_lora
+
+        def once(unet, n):
+            if unet is not None:
+                eng.forge_objects_after_applying_lora = saved.shallow_copy()
+                eng.forge_objects_after_applying_lora.unet = unet
+            try:
+                pr = processing.StableDiffusionProcessingTxt2Img(sd_model=eng, c=c1, uc=u1, seed=1, sampler_name="Euler", batch_size=b, steps=n,
+                                                                 cfg_scale=7.0, width=width, height=height, do_decode=False)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                lat = processing.process_images(pr).latents
+                e1.record()
+                torch.cuda.synchronize()
+                return e0.elapsed_time(e1), lat
+            finally:
+                eng.forge_objects_after_applying_lora = saved
+                eng.forge_objects = saved.shallow_copy()
+        try:
+            for unet in variants.values():    # priming (arena, caches, graphs)
+                once(unet, 4)
+        finally:
+            ops.attn_value_rows = real
+        if set(variants) != {"plain", "pag_native", "pag_python"}:      # a single route, for a profiler: timed jobs, no comparison line
+            for k, unet in variants.items():
+                print(json.dumps({"case": "Perturbed-Attention Guidance, route " + k, "ms_per_step": [round(once(unet, a.steps)[0] / a.steps, 2) for _ in range(rounds)]}),
+                      flush=True)
+            return
+        depth = cfg["transformer_depth_middle"]
+        per_call = calls[:depth]              # one UNet call: one copy per transformer block of the middle block
+        ms = {k: [] for k in variants}
+        finite = True
+        for _ in range(rounds):
+            for k, unet in variants.items():
+                once(unet, 2)             # a job on another route came before: what follows a change of route is not timed
+                dt, lat = once(unet, a.steps)
+                ms[k].append(round(dt / a.steps, 2))
+                finite = finite and bool(torch.isfinite(lat).all())
+        med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+        vt_shape, out_shape, kw = per_call[0]
+        vt, out = torch.randn(vt_shape, device=dev).half(), torch.empty(out_shape, device=dev, dtype=torch.float16)
+        nbytes = 2 * kw["count"] * kw["n"] * kw["hd"]
+        src, dst = torch.empty(nbytes // 2, device=dev, dtype=torch.float16), torch.empty(nbytes // 2, device=dev, dtype=torch.float16)
+
+        def timed(fn):
+            t = []
+            for i in range(23):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                torch.cuda.synchronize()
+                if i >= 3:
+                    t.append(e0.elapsed_time(e1))
+            return sorted(t)[len(t) // 2]
+        copy_ms = timed(lambda: real(vt, out, **kw))
+        plain_copy_ms = timed(lambda: dst.copy_(src))
+        print(json.dumps({"case": f"Perturbed-Attention Guidance (scale {scale}, no attenuation, every step guided): plain vs native (third group of rows, "
+                                  "captured graph) vs the Python route (post-CFG function + attn1 replace patch: a second, eager model call)",
+                          "sampler": "Euler", "steps": a.steps, "rounds": rounds, "ms_per_step": med, "ms_per_step_rounds": ms,
+                          "native_over_plain": round(med["pag_native"] / med["plain"], 3), "python_over_native": round(med["pag_python"] / med["pag_native"], 3),
+                          "copy_calls_per_unet_call": len(per_call), "copy_call": {"vt": list(vt_shape), "out": list(out_shape), **kw},
+                          "copy_kernel_ms": round(copy_ms, 4), "copy_kernel_GBps_read_plus_write": round(2 * nbytes / copy_ms / 1e6, 1),
+                          "device_copy_same_bytes_ms": round(plain_copy_ms, 4), "device_copy_GBps_read_plus_write": round(2 * nbytes / plain_copy_ms / 1e6, 1),
+                          "copy_kernels_share_of_native_step": round(len(per_call) * copy_ms / med["pag_native"], 5),
+                          "finite": finite, "shape": list(lat.shape)}), flush=True)
+
     if "one" in what:
         run(f"{width}x{height}", sampler="Euler")
+    if "pag" in what:
+        pag_leg()
     if "dynthresh" in what:
         dynthresh_leg()
     if "freeu" in what:
