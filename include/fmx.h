@@ -45,6 +45,9 @@
  *   fmx_conv3x3_c64_f16 / fmx_taesd_pack_latent / fmx_latent_rgb
  *                          the TAESD decoder modules/sd_vae_taesd.py:16-44 (live previews modules/sd_samplers_common.py:36-93,123-128 and the "TAESD"
  *                          decode method) ; cheap_approximation modules/sd_vae_approx.py:73-74
+ *   fmx_conv3x3_dense_f16 / fmx_esrgan_pack_image / fmx_esrgan_unpack_image
+ *                          the ESRGAN-family image upscalers of the hires pass (RRDBNet nf 64, gc 32, x4): modules/esrgan_model.py,
+ *                          modules/upscaler_utils.py:14-35,51-88, modules/processing.py:1466-1489
  *   fmx_*_bf16             the bfloat16 build of the Flux path's kernels (last section)
  *   fmx_gguf_dequant_*     GGUF checkpoints: backend/utils.py:27-31 (load_torch_file), backend/operations_gguf.py (dequantize_tensor,
  *                          quants_mapping), backend/loader.py:181-211 (replace_state_dict), packages_3rdparty/gguf/quants.py (dequantize_blocks)
@@ -467,6 +470,33 @@ int fmx_conv3x3_narrow_gn_silu_f16(const void* x, int32_t n, int32_t h, int32_t 
  * of the weight in LDS and walks 8 x 32-pixel output tiles, whose input patches are staged once each (double-buffered) instead of gathered nine times. */
 int fmx_conv3x3_c64_f16(const void* x, int32_t n, int32_t h, int32_t w, int32_t cin, const void* wgt, const void* bias, int32_t cout, const void* residual,
                         int64_t ld_res, int32_t relu, int32_t up2x, void* out, int64_t ld_out, void* stream);
+/* 3x3 convolution (stride 1, zero padding 1) of the ESRGAN residual dense block: cin in {64, 96, 128, 160, 192} -> cout in {32, 64}, LeakyReLU and up to two
+ * scaled residuals in the epilogue.  New symbols, the ABI number does not move.
+ *   out[m][o] = E(bias[o] + sum_{ky,kx,c<cin} wgt[o][ky][kx][c] * xin[pixel(m) + (ky-1, kx-1)][c])                  (xin zero outside the oh x ow image)
+ *   E(f): f = f >= 0 ? f : slope * f;  if res1: f = alpha * f + res1[m][o];  if res2: f = beta * f + res2[m][o];  ONE rounding to fp16
+ * x fp16 NHWC with pixel pitch ld_x >= cin: the kernel reads channels [0, cin) of each pixel and nothing else; wgt [cout][ky][kx][cin] (the GEMM entry's
+ * layout); bias [cout] or null; res1 / res2 [n*oh*ow][ld_res*] or null (res2 requires res1); slope = 1 is no activation; up2x 0: (oh, ow) = (h, w) and
+ * xin = x; up2x 1 (only for cin == cout == 64): (oh, ow) = (2h, 2w) and xin[Y][X] = x[Y >> 1][X >> 1] as in fmx_conv3x3_c64_f16; out [n*oh*ow][ld_out].
+ * fp32 accumulation over all of K = 9 cin, one rounding.  The kernel writes exactly (m, o < cout); row and column tails are masked.
+ * IN-PLACE WINDOW FORM: out may be a column window of x's own buffer (out = x + col, ld_out = ld_x) provided [col, col + cout) is disjoint from [0, cin);
+ * res1 / res2 may be read-only windows of the same buffer, x's own first columns included.  A dense block then lives in ONE 192-channel buffer
+ * [x | x1 | x2 | x3 | x4] with no concatenation: conv_k reads [0, 64 + 32 (k-1)) and writes the next 32 columns.  conv5 produces the NEXT block's first 64
+ * columns, which other tiles' halos still read as input: it must write ANOTHER such buffer than the one it reads (the buffers rotate).  out may be res1
+ * or res2 itself (same address and pitch): every element is read by the lane that then writes it.  An out inside x's rows that overlaps the input
+ * columns, has another pitch or comes with up2x is FMX_E_BADARG.
+ * Any other cin / cout, res2 without res1, ld_x < cin or not a multiple of 8, ld_out / ld_res* < cout or not multiples of 4: FMX_E_BADARG before any
+ * launch.  x and wgt 16-byte aligned; out / res1 / res2 / bias 8-byte aligned.  A direct kernel: one persistent workgroup per CU walks 8 x 32-pixel
+ * output tiles; the K loop stages 32-channel chunks of the input patch and of the weight (neither fits LDS whole), double-buffered. */
+int fmx_conv3x3_dense_f16(const void* x, int64_t ld_x, int32_t n, int32_t h, int32_t w, int32_t cin, const void* wgt, const void* bias, int32_t cout,
+                          float slope, const void* res1, int64_t ld_res1, float alpha, const void* res2, int64_t ld_res2, float beta, int32_t up2x, void* out,
+                          int64_t ld_out, void* stream);
+/* ESRGAN input (modules/upscaler_utils.py:14-19 pil_image_to_torch_bgr, then the cast to the model's type): img uint8 RGB [npix][3] -> fp16 [npix][64],
+ * channels 0..2 = lut[B], lut[G], lut[R], channels 3..63 zeros.  lut: DEVICE table of 256 fp16 values the host builds as fp16(float64(v) / 255).
+ * out 16-byte aligned. */
+int fmx_esrgan_pack_image(const void* img, const void* lut, int64_t npix, void* out, void* stream);
+/* ESRGAN output (modules/upscaler_utils.py:22-35 torch_bgr_to_pil_image): y fp16 [npix][ld], channels 0..2 = B, G, R -> uint8 RGB [npix][3] =
+ * rint(255.0f * clamp(float(v), 0, 1)), ties to even (numpy's round) */
+int fmx_esrgan_unpack_image(const void* y, int64_t ld, int64_t npix, void* out, void* stream);
 /* TAESD input (modules/sd_vae_taesd.py:20-23 Clamp behind modules/sd_samplers_common.py:60 `sample.to(devices.dtype)`): latent fp32 NCHW [b][c][h][w], c <= 64
  * -> tanh(round16(z) / 3) * 3 (fp32 arithmetic, one rounding) as fp16 NHWC [b*h*w][64], channels >= c zeros */
 int fmx_taesd_pack_latent(const float* z, int32_t b, int32_t c, int32_t h, int32_t w, void* out, void* stream);

@@ -164,6 +164,10 @@ for _n in ("fmx_vae_pack_latent", "fmx_vae_unpack_image", "fmx_vae_sample_poster
 # the TAESD decoder (new symbols, the ABI number does not move)
 SIGNATURES["fmx_conv3x3_c64_bf16"] = SIGNATURES["fmx_conv3x3_c64_f16"]
 SIGNATURES["fmx_taesd_pack_latent_bf16"] = SIGNATURES["fmx_taesd_pack_latent"]
+# the ESRGAN upscalers (csrc/fmx_conv_dense.hip): new symbols, the ABI number does not move
+SIGNATURES["fmx_conv3x3_dense_f16"] = [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _f32, _vp, _i64, _f32, _vp, _i64, _f32, _i32, _vp, _i64, _vp]
+SIGNATURES["fmx_esrgan_pack_image"] = [_vp, _vp, _i64, _vp, _vp]
+SIGNATURES["fmx_esrgan_unpack_image"] = [_vp, _i64, _i64, _vp, _vp]
 # GGUF block dequantisation at load time (qtype, blocks, out, n_elements, stream): new symbols, the ABI number does not move
 for _n in ("fmx_gguf_dequant_f16", "fmx_gguf_dequant_bf16"):
     SIGNATURES[_n] = [_i32, _vp, _vp, _i64, _vp]

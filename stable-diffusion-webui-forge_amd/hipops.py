@@ -1021,11 +1021,13 @@ def vae_sample_posterior(moments, ld, noise, lc, scale=1.0, shift=0.0, out=None)
     return out
 
 
-def count_nonfinite(x):
-    """-> python int: inf / NaN values in the fp16 tensor x (contiguous).  One device sync -- the caller decides on the host (VAE overflow guard)."""
+def count_nonfinite(x, cnt=None):
+    """-> python int: inf / NaN values in the fp16 tensor x (contiguous).  One device sync -- the caller decides on the host (VAE overflow guard).
+    cnt: an int32 device scalar to count into (a caller that must not allocate hands one over)."""
     _check_f16(x)
     assert x.is_contiguous()
-    cnt = torch.empty(1, dtype=torch.int32, device=x.device)
+    if cnt is None:
+        cnt = torch.empty(1, dtype=torch.int32, device=x.device)
     _lib.check(_lib.lib().fmx_count_nonfinite_f16(_p(x), x.numel(), _p(cnt), stream_ptr()), "fmx_count_nonfinite_f16")
     return int(cnt.item())
 
@@ -1072,6 +1074,81 @@ def conv3x3_c64(x, wgt, bias=None, *, residual=None, relu=False, up2x=False, out
                          nbytes=2.0 * 64 * (n * h * w + m * (2 if residual is not None else 1)))
     else:
         run()
+    return out
+
+
+def conv3x3_dense(x, cin, wgt, bias=None, *, slope=1.0, res1=None, alpha=1.0, res2=None, beta=1.0, up2x=False, out=None):
+    """3x3 convolution of the ESRGAN dense block (fmx_conv3x3_dense_f16): x fp16 [n, h, w, >= cin] with unit channel stride and dense pixels of pitch
+    x.stride(2) (a channel window of a wider NHWC buffer), of which channels [0, cin) are read; wgt [cout, 9 * cin] in the GEMM's tap-major layout, cout 32
+    or 64 -> [n * oh * ow, cout] = round(E(bias + conv)), E(f) = leaky(f, slope), then alpha * f + res1, then beta * f + res2.  out / res1 / res2 are 2-D
+    row-strided windows; out may be columns [col, col + cout) of x's own buffer when they are disjoint from [0, cin) (include/fmx.h: in-place window form)."""
+    _check_f16(x, wgt, bias, res1, res2, out)
+    n, h, w, _ = x.shape
+    ld_x = x.stride(2)
+    if x.stride(3) != 1 or x.stride(1) != w * ld_x or x.stride(0) != h * w * ld_x or x.shape[3] < cin:
+        raise ValueError("conv3x3_dense: x must be [n, h, w, >= cin] with dense pixels of one pitch")
+    cout = wgt.shape[0]
+    if wgt.dim() != 2 or wgt.shape[1] != 9 * cin or not wgt.is_contiguous():
+        raise ValueError(f"conv3x3_dense: wgt must be a contiguous [cout, {9 * cin}] matrix, got {tuple(wgt.shape)}")
+    m = n * (h << int(up2x)) * (w << int(up2x))
+    if out is None:
+        out = empty((m, cout), torch.float16, x.device)
+    for t in (out, res1, res2):
+        if t is not None and (t.dim() != 2 or t.shape[0] != m or t.shape[1] < cout or t.stride(1) != 1):
+            raise ValueError("conv3x3_dense: out / res1 / res2 must be [n * oh * ow, >= cout] with unit column stride")
+
+    def run():
+        _lib.check(_lib.lib().fmx_conv3x3_dense_f16(_p(x), ld_x, n, h, w, cin, _p(wgt), _p(bias), cout, float(slope), _p(res1),
+                                                    res1.stride(0) if res1 is not None else 0, float(alpha), _p(res2), res2.stride(0) if res2 is not None else 0,
+                                                    float(beta), int(bool(up2x)), _p(out), out.stride(0), stream_ptr()), "fmx_conv3x3_dense_f16")
+    if _profiler is not None:
+        nres = (res1 is not None) + (res2 is not None)
+        _profiler.launch("conv3x3_dense", 2.0 * m * 9 * cin * cout, run, tag=f"cin={cin} cout={cout} up2x={int(up2x)}",
+                         nbytes=2.0 * (n * h * w * cin + m * cout * (1 + nres)))
+    else:
+        run()
+    return out
+
+
+_esrgan_luts = {}
+
+
+def esrgan_lut(device):
+    """the 256-entry fp16 table fp16(float64(v) / 255) of fmx_esrgan_pack_image, one per device"""
+    device = torch.device(device)
+    key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+    lut = _esrgan_luts.get(key)
+    if lut is None:
+        lut = (torch.arange(256, dtype=torch.float64) / 255).to(torch.float16).to(device)
+        _esrgan_luts[key] = lut
+    return lut
+
+
+def esrgan_pack_image(img, out=None):
+    """uint8 RGB [n, h, w, 3] (contiguous, device) -> fp16 NHWC [n, h, w, 64]: channels 0..2 = B, G, R as fp16(v / 255), the rest zeros (fmx_esrgan_pack_image)"""
+    if img.dtype != torch.uint8 or not img.is_cuda or not img.is_contiguous() or img.dim() != 4 or img.shape[3] != 3:
+        raise TypeError("esrgan_pack_image expects a contiguous uint8 device tensor [n, h, w, 3]")
+    n, h, w, _ = img.shape
+    if out is None:
+        out = empty((n, h, w, 64), torch.float16, img.device)
+    _check_f16(out)
+    if not out.is_contiguous() or out.numel() != n * h * w * 64:
+        raise ValueError("esrgan_pack_image: out must be a contiguous [n, h, w, 64] tensor")
+    _lib.check(_lib.lib().fmx_esrgan_pack_image(_p(img), _p(esrgan_lut(img.device)), n * h * w, _p(out), stream_ptr()), "fmx_esrgan_pack_image")
+    return out
+
+
+def esrgan_unpack_image(y, out=None):
+    """fp16 [npix, ld] (unit column stride), columns 0..2 = B, G, R -> uint8 RGB [npix, 3] = rint(255 * clamp(v, 0, 1)), ties to even (fmx_esrgan_unpack_image)"""
+    _check_f16(y)
+    if y.dim() != 2 or y.stride(1) != 1 or y.shape[1] < 3:
+        raise ValueError("esrgan_unpack_image: y must be [npix, >= 3] with unit column stride")
+    npix = y.shape[0]
+    if out is None:
+        out = empty((npix, 3), torch.uint8, y.device)
+    if out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != npix * 3:
+        raise ValueError("esrgan_unpack_image: out must be a contiguous uint8 [npix, 3] tensor")
+    _lib.check(_lib.lib().fmx_esrgan_unpack_image(_p(y), y.stride(0), npix, _p(out), stream_ptr()), "fmx_esrgan_unpack_image")
     return out
 
 

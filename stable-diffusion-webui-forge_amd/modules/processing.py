@@ -163,8 +163,8 @@ class StableDiffusionProcessingTxt2Img:
             self.hr_scheduler = self.scheduler
         modes = latent_upscale.latent_upscale_modes
         self.latent_scale_mode = modes.get(self.hr_upscaler, None) if self.hr_upscaler is not None else modes[latent_upscale.latent_upscale_default_mode]
-        if self.latent_scale_mode is None:
-            raise NotImplementedError(f"hires upscaler '{self.hr_upscaler}': only the latent upscalers {list(modes)} are on the native path")
+        if self.latent_scale_mode is None and not any(x.name == self.hr_upscaler for x in shared.sd_upscalers):      # :1319-1321
+            raise Exception(f"could not find upscaler named {self.hr_upscaler}")
         self.calculate_target_resolution()
 
     def sample(self, conditioning, unconditional_conditioning, seeds, subseeds=None, subseed_strength=0.0, prompts=None):
@@ -178,18 +178,27 @@ class StableDiffusionProcessingTxt2Img:
         return self.sample_hr_pass(samples, None, seeds, subseeds, subseed_strength, prompts)
 
     def sample_hr_pass(self, samples, decoded_samples, seeds, subseeds=None, subseed_strength=0.0, prompts=None):
-        """processing.py:1430-1536 for the latent upscalers: resize the first-pass latent, fresh noise from a new ImageRNG with the same
-        seeds, img2img pass with the hires sampler / scheduler / CFG / conds.  Returns the hires LATENT (the reference returns it decoded,
-        :1531; here process_images_inner decodes it like any other sample)."""
+        """processing.py:1430-1536: resize the first-pass latent (latent upscalers) or decode, upscale the IMAGE with an entry of
+        shared.sd_upscalers and encode it again (:1466-1489), then fresh noise from a new ImageRNG with the same seeds and the img2img pass with
+        the hires sampler / scheduler / CFG / conds.  Returns the hires LATENT (the reference returns it decoded, :1531; here
+        process_images_inner decodes it like any other sample)."""
         from . import latent_upscale
         if shared.state.interrupted:
             return samples
         self.is_hr_pass = True
         try:
             self.sampler = sd_samplers.create_sampler(self.hr_sampler_name or self.sampler_name, self.sd_model)
-            samples = latent_upscale.interpolate(samples.contiguous(), (self.hr_upscale_to_y // 8, self.hr_upscale_to_x // 8),
-                                                 mode=self.latent_scale_mode["mode"], antialias=self.latent_scale_mode["antialias"])
-            image_conditioning = self.txt2img_image_conditioning(samples)
+            if self.latent_scale_mode is not None:
+                samples = latent_upscale.interpolate(samples.contiguous(), (self.hr_upscale_to_y // 8, self.hr_upscale_to_x // 8),
+                                                     mode=self.latent_scale_mode["mode"], antialias=self.latent_scale_mode["antialias"])
+                image_conditioning = self.txt2img_image_conditioning(samples)
+            else:
+                if decoded_samples is None:
+                    decoded_samples = decode_first_stage(self.sd_model, samples)
+                decoded_samples = self.upscale_decoded(decoded_samples)
+                from .sd_samplers_common import approximation_indexes, images_tensor_to_samples
+                samples = images_tensor_to_samples(decoded_samples, approximation_indexes.get(shared.opts.sd_vae_encode_method), self.sd_model)
+                image_conditioning = self.img2img_image_conditioning(decoded_samples, samples)
             ty, tx = self.truncate_y, self.truncate_x
             samples = samples[:, :, ty // 2:samples.shape[2] - (ty + 1) // 2, tx // 2:samples.shape[3] - (tx + 1) // 2].contiguous()
             self.rng = rng.ImageRNG(tuple(samples.shape[1:]), self.seeds, subseeds=getattr(self, "subseeds", None), subseed_strength=self.subseed_strength,
@@ -205,6 +214,21 @@ class StableDiffusionProcessingTxt2Img:
                                                image_conditioning=image_conditioning)
         finally:
             self.is_hr_pass = False
+
+
+    def upscale_decoded(self, decoded_samples):
+        """:1467-1483: decoded first-pass images [B, 3, H, W] in [-1, 1] -> the upscaled images [B, 3, target H, target W] in [0, 1], fp32 on the
+        model's device.  255 x is TRUNCATED to uint8 here, as the reference does (`astype(np.uint8)`)."""
+        from PIL import Image
+        from . import images
+        lowres_samples = torch.clamp((decoded_samples.float() + 1.0) / 2.0, min=0.0, max=1.0)
+        batch_images = []
+        for x_sample in lowres_samples:
+            x_sample = 255. * np.moveaxis(x_sample.cpu().numpy(), 0, 2)
+            image = Image.fromarray(x_sample.astype(np.uint8))
+            image = images.resize_image(0, image, self.hr_upscale_to_x, self.hr_upscale_to_y, upscaler_name=self.hr_upscaler)
+            batch_images.append(np.moveaxis(np.array(image).astype(np.float32) / 255.0, 2, 0))
+        return torch.from_numpy(np.array(batch_images)).to(self.sd_model.device, dtype=torch.float32)
 
 
 @dataclass

@@ -16,6 +16,7 @@ opts = SimpleNamespace(
     eta_ancestral=1.0, eta_ddim=0.0, sigma_min=0.0, sigma_max=0.0, rho=0.0, s_churn=0.0, s_tmin=0.0, s_tmax=0.0, s_noise=1.0,
     uni_pc_variant="bh1", uni_pc_skip_type="time_uniform", uni_pc_order=3, uni_pc_lower_order_final=True, beta_dist_alpha=0.6, beta_dist_beta=0.6, forge_try_reproduce="None", sd_vae_decode_method="Full",
     sd_vae_encode_method="Full", live_previews_enable=False, show_progress_every_n_steps=10, show_progress_type="Approx NN",
+    ESRGAN_tile=192, ESRGAN_tile_overlap=8, upscaler_for_img2img=None,  # modules/shared_options.py:102-103,108
 )
 
 
@@ -57,6 +58,7 @@ class State:
 
 state = State()
 sd_model = None
+sd_upscalers = []                    # UpscalerData entries by name (modules/shared.py sd_upscalers); modules/esrgan_model.register() fills it
 device = None
 models_path = "models"               # modules/paths_internal.py models_path: TAESD weights are looked up in <models_path>/VAE-taesd (modules/sd_vae_taesd.py)
 parallel_processing_allowed = False  # shared.py:60-ish of the reference: True there when a UI thread polls State.set_current_image; here the sampler makes the previews itself
