@@ -3,7 +3,7 @@
 // of them at the full image size, where the implicit GEMM would gather every input pixel nine times (fmx_conv_patch.hip is the same finding at 128 channels).
 //   * a workgroup (4 waves, ONE per CU: it owns the CU's LDS) is persistent: it loads all nine taps of the weight -- 64 x 9 x 64 x 2 = 73 728 bytes -- into
 //     LDS once and then walks output tiles of 8 rows x 32 pixels (tile index blockIdx.x, + gridDim.x, ...), all 64 output channels each;
-//   * the 10 x 34-pixel input patch of a tile (128-byte pixels, 16-byte chunk c of patch column q at chunk c ^ ((q >> 1) & 7), zeros outside the image) is
+//   * the 10 x 34-pixel input patch of a tile (128-byte pixels in the swizzled format of fmx_conv_direct.hpp, zeros outside the image) is
 //     double-buffered: the global loads of the NEXT tile's patch are issued before the MFMA loop of this one and written to the other LDS buffer after its
 //     epilogue, so one barrier per tile; 73 728 + 2 x 43 520 = 160 768 bytes of the CU's 163 840;
 //   * with up2x the patch is staged from the half-resolution source, pixel (Y >> 1, X >> 1) for upsampled (Y, X): the upsampled tensor never exists, the layer
@@ -11,12 +11,11 @@
 //   * the nine taps read their shifted pixels from the patch (MFMA-B operand of v_mfma_f32_16x16x32: 16 neighbouring pixels of a row), the weights are the A
 //     operand; a wave owns 2 rows = 64 pixels x 64 channels (4 x 4 accumulator blocks, 8 fragment reads per 16 MFMAs, no barrier inside a tile);
 //   * epilogue in the accumulator layout (a lane holds 4 consecutive output channels of a pixel): + bias (+ residual), ReLU, ONE rounding, 8-byte stores.
-#include "fmx_common.hpp"
+// Tile, accumulator layout, LDS format, tap step and patch items: fmx_conv_direct.hpp.
+#include "fmx_conv_direct.hpp"
 
 namespace {
 
-constexpr int TH = 8, TW = 32;                 // output tile
-constexpr int PH = TH + 2, PW = TW + 2;        // staged patch (1-pixel halo)
 constexpr int CH = 64;                         // channels in and out: 128-byte pixels in LDS
 constexpr int PATCH_BYTES = PH * PW * CH * 2;  // 43 520
 constexpr int TAP_BYTES = CH * CH * 2;         // 8 192: one tap, [out channel][in channel]
@@ -47,54 +46,37 @@ __global__ __launch_bounds__(256, 1) void conv3x3_c64_kernel(const C64Params p) 
   const int h = p.h, w = p.w, oh = p.oh, ow = p.ow, up = p.up;
   const int tiles_per_img = p.tiles_x * p.tiles_y;
 
-  // ---- weights, once: row o of tap t at t * 8192 + o * 128, its 16-byte chunk c at chunk c ^ ((o >> 1) & 7) -----------------------------------------
+  // ---- weights, once: row o of tap t at t * 8192 + o * 128, swizzled ----------------------------------------------------------------------------------
 #pragma unroll
   for (int it = 0; it < W_ITEMS / 256; ++it) {
     const int i = tid + it * 256;
     const int o = i / 72, rem = i - o * 72, t = rem >> 3, c = rem & 7;
-    *reinterpret_cast<f16x8*>(smem + t * TAP_BYTES + o * 128 + ((c ^ ((o >> 1) & 7)) << 4)) = *reinterpret_cast<const f16x8*>(p.wgt + (long)i * 8);
+    *reinterpret_cast<f16x8*>(smem + t * TAP_BYTES + swz_off(o, o, c)) = *reinterpret_cast<const f16x8*>(p.wgt + (long)i * 8);
   }
 
   // ---- input patch of a tile: global -> registers (load_patch), registers -> LDS (store_patch) ------------------------------------------------------
   const int cc = tid & 7;                                          // this thread's 16-byte channel octet, in every item
   f16x8 v[ITERS];
   auto load_patch = [&](int tile) __attribute__((always_inline)) {
-    const int img = tile / tiles_per_img, tin = tile - img * tiles_per_img;
-    const int ty = tin / p.tiles_x, tx = tin - ty * p.tiles_x;
-    const int y0 = ty * TH - 1, x0 = tx * TW - 1;
+    const TilePos t = tile_decode(tile, p.tiles_x, tiles_per_img);
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
-      const int pi = (tid >> 3) + it * 32;                         // patch pixel
-      const int pr = pi / PW, q = pi - pr * PW;
-      const int gy = y0 + pr, gx = x0 + q;                         // in the (upsampled) image the convolution runs on
-      const bool ok = pi < PH * PW && gy >= 0 && gy < oh && gx >= 0 && gx < ow;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[it][e] = (f16)0.0f;            // the convolution's zero padding
-      if (ok) v[it] = *reinterpret_cast<const f16x8*>(p.x + (((long)img * h + (gy >> up)) * w + (gx >> up)) * CH + cc * 8);
+      const PatchItem i = patch_item<8>(tid, it, t.ty * TH, t.tx * TW);
+      v[it] = zero_octet();                                        // the convolution's zero padding
+      if (i.pi < PH * PW && in_image(i, oh, ow)) v[it] = *reinterpret_cast<const f16x8*>(p.x + patch_src_pixel(i, t.img, h, w, up) * CH + cc * 8);
     }
   };
   auto store_patch = [&](char* patch) __attribute__((always_inline)) {
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
-      const int pi = (tid >> 3) + it * 32;
-      const int pr = pi / PW, q = pi - pr * PW;
-      if (pi < PH * PW) *reinterpret_cast<f16x8*>(patch + pi * (CH * 2) + ((cc ^ ((q >> 1) & 7)) << 4)) = v[it];
+      const PatchItem i = patch_item<8>(tid, it, 0, 0);             // its place in the patch only
+      if (i.pi < PH * PW) *reinterpret_cast<f16x8*>(patch + swz_off(i.pi, i.q, cc)) = v[it];
     }
   };
 
   f32x4 bsum[4];
-#pragma unroll
-  for (int cb = 0; cb < 4; ++cb) {
-    bsum[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (p.bias) {
-      const f16x4 b4 = *reinterpret_cast<const f16x4*>(p.bias + cb * 16 + kg * 4);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) bsum[cb][r] = (float)b4[r];
-    }
-  }
-
-  // per-lane parts of the fragment addresses.  Weights: row cb * 16 + l16 -> swizzle key (l16 >> 1) & 7 (cb * 16 does not change it)
-  const int w_lane = l16 * 128 + ((kg ^ ((l16 >> 1) & 7)) << 4);
+  load_bias(bsum, p.bias, kg);
+  const int w_lane = w_frag_off(l16, kg);
 
   int tile = blockIdx.x;
   if (tile >= p.ntiles) return;
@@ -116,41 +98,19 @@ __global__ __launch_bounds__(256, 1) void conv3x3_c64_kernel(const C64Params p) 
 #pragma unroll
     for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-      for (int kx = 0; kx < 3; ++kx) {
-        // byte offsets; every term but the chunk bits (4-6) is a multiple of 128, so k-step 1 (logical chunks 4-7) is `^ 64`
-        const int wo = (ky * 3 + kx) * TAP_BYTES + w_lane;
-        // activations: pixel column q = (pb & 1) * 16 + l16 + kx of patch row 2 * wave + (pb >> 1) + ky; the key of (16 + q') equals the key of q'
-        const int q0 = l16 + kx;
-        const int po = ((2 * wave + ky) * PW + q0) * (CH * 2) + ((kg ^ ((q0 >> 1) & 7)) << 4);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          f16x8 wf[4], af[4];
-          const char* wks = smem + (wo ^ (ks * 64));
-          const char* pks = patch + (po ^ (ks * 64));
-#pragma unroll
-          for (int cb = 0; cb < 4; ++cb) wf[cb] = *reinterpret_cast<const f16x8*>(wks + cb * 2048);
-#pragma unroll
-          for (int pb = 0; pb < 4; ++pb) af[pb] = *reinterpret_cast<const f16x8*>(pks + ((pb >> 1) * PW + (pb & 1) * 16) * (CH * 2));
-#pragma unroll
-          for (int pb = 0; pb < 4; ++pb)
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb) acc[pb][cb] = FMX_MFMA_16x16x32(wf[cb], af[pb], acc[pb][cb]);
-        }
-      }
+      for (int kx = 0; kx < 3; ++kx)
+        tap_mfma(acc, smem, (ky * 3 + kx) * TAP_BYTES + w_lane, patch, p_frag_off(wave, l16, kg, ky, kx));
 
-    // ---- epilogue: lane (l16, kg) of block (pb, cb) holds output channels cb * 16 + kg * 4 + 0..3 of pixel (row 2 * wave + (pb >> 1), column (pb & 1) * 16 + l16) ----
+    // ---- epilogue in the accumulator layout ----
     {
-      const int img = tile / tiles_per_img, tin = tile - img * tiles_per_img;
-      const int ty = tin / p.tiles_x, tx = tin - ty * p.tiles_x;
+      const TilePos t = tile_decode(tile, p.tiles_x, tiles_per_img);
 #pragma unroll
       for (int pb = 0; pb < 4; ++pb) {
-        const int oy = ty * TH + 2 * wave + (pb >> 1), ox = tx * TW + (pb & 1) * 16 + l16;
-        const bool ok = oy < oh && ox < ow;
-        const long m = ((long)img * oh + oy) * ow + ox;
+        const auto [ok, m] = out_pixel(t, wave, pb, l16, oh, ow);
         f16x4 rv[4];
         if (p.res && ok) {
 #pragma unroll
-          for (int cb = 0; cb < 4; ++cb) rv[cb] = *reinterpret_cast<const f16x4*>(p.res + m * p.ld_res + cb * 16 + kg * 4);
+          for (int cb = 0; cb < 4; ++cb) rv[cb] = *reinterpret_cast<const f16x4*>(p.res + m * p.ld_res + acc_chan(cb, kg));
         }
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb) {
@@ -162,7 +122,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_c64_kernel(const C64Params p) 
             if (p.relu) f = fmaxf(f, 0.0f);
             o[r] = (f16)f;
           }
-          if (ok) *reinterpret_cast<f16x4*>(p.out + m * p.ld_out + cb * 16 + kg * 4) = o;
+          if (ok) *reinterpret_cast<f16x4*>(p.out + m * p.ld_out + acc_chan(cb, kg)) = o;
         }
       }
     }
@@ -182,21 +142,13 @@ extern "C" int fmx_conv3x3_c64_f16(const void* x, int32_t n, int32_t h, int32_t 
   FMX_REQUIRE(n > 0 && h > 0 && w > 0, "conv3x3_c64: bad geometry");
   FMX_REQUIRE((relu == 0 || relu == 1) && (up2x == 0 || up2x == 1), "conv3x3_c64: relu and up2x are 0 or 1");
   FMX_REQUIRE(ld_out >= CH && (ld_out % 4) == 0 && (!residual || (ld_res >= CH && (ld_res % 4) == 0)), "conv3x3_c64: bad leading dimensions");
-  FMX_REQUIRE(fmx_aligned16(x) && fmx_aligned16(wgt) && (reinterpret_cast<uintptr_t>(out) & 7u) == 0 &&
-                  (!residual || (reinterpret_cast<uintptr_t>(residual) & 7u) == 0) && (!bias || (reinterpret_cast<uintptr_t>(bias) & 7u) == 0),
-              "conv3x3_c64: operand alignment");
+  FMX_REQUIRE(fmx_aligned16(x) && fmx_aligned16(wgt) && aligned8(out) && aligned8(residual) && aligned8(bias), "conv3x3_c64: operand alignment");
   const int oh = h << up2x, ow = w << up2x;
-  const int tiles_x = (ow + TW - 1) / TW, tiles_y = (oh + TH - 1) / TH;
-  const long ntiles = (long)n * tiles_x * tiles_y;
-  FMX_REQUIRE(ntiles < (1L << 31), "conv3x3_c64: too many tiles for one launch (split the batch)");
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-      return fmx_set_error(FMX_E_UNSUPPORTED, "conv3x3_c64: cannot read the device's CU count");
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_c64_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    cus = v;
-  }
+  const TileGrid g = tile_grid(n, oh, ow);
+  FMX_REQUIRE(g.one_launch(), "conv3x3_c64: too many tiles for one launch (split the batch)");
+  const unsigned grid = persistent_grid(g.ntiles);   // one persistent workgroup per CU
+  if (!grid) return fmx_set_error(FMX_E_UNSUPPORTED, "conv3x3_c64: cannot read the device's CU count");
+  lds_ceiling_once<&conv3x3_c64_kernel, SMEM>();
   C64Params p;
   p.x = (const f16*)x;
   p.wgt = (const f16*)wgt;
@@ -205,8 +157,7 @@ extern "C" int fmx_conv3x3_c64_f16(const void* x, int32_t n, int32_t h, int32_t 
   p.ld_res = ld_res;
   p.out = (f16*)out;
   p.ld_out = ld_out;
-  p.h = h; p.w = w; p.oh = oh; p.ow = ow; p.up = up2x; p.relu = relu; p.tiles_x = tiles_x; p.tiles_y = tiles_y; p.ntiles = (int)ntiles;
-  const unsigned grid = (unsigned)(ntiles < cus ? ntiles : cus);   // one persistent workgroup per CU
+  p.h = h; p.w = w; p.oh = oh; p.ow = ow; p.up = up2x; p.relu = relu; p.tiles_x = g.tiles_x; p.tiles_y = g.tiles_y; p.ntiles = (int)g.ntiles;
   hipLaunchKernelGGL(conv3x3_c64_kernel, dim3(grid), dim3(256), SMEM, (hipStream_t)stream, p);
   FMX_LAUNCH_CHECK("fmx_conv3x3_c64_f16");
   return FMX_OK;

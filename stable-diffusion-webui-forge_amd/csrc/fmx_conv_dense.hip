@@ -7,7 +7,7 @@
 // 64 columns).  conv5 writes the NEXT block's first 64 columns, which other tiles' halos still read: it must go to the OTHER of two such buffers, which
 // then ping-pong.  The entry point refuses an `out` that lies inside x's rows and overlaps [0, cin).
 //
-//   * fmx_conv_c64.hip is the template: a persistent workgroup (4 waves, ONE per CU) walks 8 x 32-pixel output tiles, a wave owns 2 rows = 64 pixels x all
+//   * tile and accumulator layout are those of fmx_conv_direct.hpp, the walk is fmx_conv_c64.hip's: a persistent workgroup (4 waves, ONE per CU) walks 8 x 32-pixel output tiles, a wave owns 2 rows = 64 pixels x all
 //     cout channels (4 x cout/16 accumulator blocks of v_mfma_f32_16x16x32, weights the A operand, 16 neighbouring pixels of a patch row the B operand);
 //   * the full weight (up to 9 x 192 x 64 x 2 = 221 184 bytes) and a 192-channel 10 x 34 patch (130 560) do not fit the CU's LDS, so the K loop walks the
 //     input channels in chunks of 32: a STAGE is (the 10 x 34 x 32-channel patch chunk, the 9 x cout x 32 weight chunk), 22 528 + 36 864 bytes, double
@@ -19,12 +19,10 @@
 //   * the accumulators stay in fp32 across all chunks; epilogue in the accumulator layout (a lane holds 4 consecutive output channels of a pixel):
 //     + bias, LeakyReLU, alpha * f + res1, beta * f + res2, ONE rounding, 8-byte stores, row / column tails masked.
 // The same file carries the two pixel kernels of the upscaler's ends (fmx_esrgan_pack_image, fmx_esrgan_unpack_image).
-#include "fmx_common.hpp"
+#include "fmx_conv_direct.hpp"
 
 namespace {
 
-constexpr int TH = 8, TW = 32;                  // output tile
-constexpr int PH = TH + 2, PW = TW + 2;         // staged patch (1-pixel halo)
 constexpr int CK = 32;                          // input channels per stage: one k-step of the MFMA, 4 octets
 constexpr int PLANE = 352;                      // slots per octet plane of the patch: PH * PW = 340 rounded up to a multiple of 16
 constexpr int PATCH_BYTES = 4 * PLANE * 16;     // 22 528
@@ -64,9 +62,8 @@ __global__ __launch_bounds__(256, 1) void conv3x3_dense_kernel(const DenseParams
   const int cc = tid & 3;                                          // this thread's channel octet of the chunk, in every patch item
   f16x8 pv[P_ITERS], wv[W_ITERS];
   auto load_stage = [&](int tile, int chunk) __attribute__((always_inline)) {
-    const int img = tile / tiles_per_img, tin = tile - img * tiles_per_img;
-    const int ty = tin / p.tiles_x, tx = tin - ty * p.tiles_x;
-    const int y0 = ty * TH - 1, x0 = tx * TW - 1;
+    const TilePos t = tile_decode(tile, p.tiles_x, tiles_per_img);
+    const int y0 = t.ty * TH - 1, x0 = t.tx * TW - 1;
     const int c0 = chunk * CK;
 #pragma unroll
     for (int it = 0; it < P_ITERS; ++it) {
@@ -74,9 +71,8 @@ __global__ __launch_bounds__(256, 1) void conv3x3_dense_kernel(const DenseParams
       const int pr = pi / PW, q = pi - pr * PW;
       const int gy = y0 + pr, gx = x0 + q;                         // in the (upsampled) image the convolution runs on
       const bool ok = pi < PH * PW && gy >= 0 && gy < oh && gx >= 0 && gx < ow;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) pv[it][e] = (f16)0.0f;           // the convolution's zero padding
-      if (ok) pv[it] = *reinterpret_cast<const f16x8*>(p.x + (((long)img * h + (gy >> up)) * w + (gx >> up)) * p.ld_x + c0 + cc * 8);
+      pv[it] = zero_octet();                                       // the convolution's zero padding
+      if (ok) pv[it] = *reinterpret_cast<const f16x8*>(p.x + (((long)t.img * h + (gy >> up)) * w + (gx >> up)) * p.ld_x + c0 + cc * 8);
     }
 #pragma unroll
     for (int it = 0; it < W_ITERS; ++it) {
@@ -100,15 +96,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_dense_kernel(const DenseParams
   };
 
   f32x4 bsum[NCB];
-#pragma unroll
-  for (int cb = 0; cb < NCB; ++cb) {
-    bsum[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (p.bias) {
-      const f16x4 b4 = *reinterpret_cast<const f16x4*>(p.bias + cb * 16 + kg * 4);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) bsum[cb][r] = (float)b4[r];
-    }
-  }
+  load_bias(bsum, p.bias, kg);
 
   int tile = blockIdx.x, chunk = 0;
   if (tile >= p.ntiles) return;
@@ -141,30 +129,26 @@ __global__ __launch_bounds__(256, 1) void conv3x3_dense_kernel(const DenseParams
         // weights: slot ((tap * 4 + kg) * COUT + cb * 16 + l16); activations: slot kg * PLANE + row * PW + column, of patch row
         // 2 * wave + (pb >> 1) + ky and column (pb & 1) * 16 + l16 + kx
         const char* wks = wts + (((ky * 3 + kx) * 4 + kg) * COUT + l16) * 16;
-        const char* pks = patch + (kg * PLANE + (2 * wave + ky) * PW + l16 + kx) * 16;
+        const char* pks = patch + (kg * PLANE + (acc_row(wave, 0) + ky) * PW + l16 + kx) * 16;
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) wf[cb] = *reinterpret_cast<const f16x8*>(wks + cb * 256);
 #pragma unroll
-        for (int pb = 0; pb < 4; ++pb) af[pb] = *reinterpret_cast<const f16x8*>(pks + ((pb >> 1) * PW + (pb & 1) * 16) * 16);
+        for (int pb = 0; pb < 4; ++pb) af[pb] = *reinterpret_cast<const f16x8*>(pks + pb_patch_pixels(pb) * 16);
 #pragma unroll
         for (int pb = 0; pb < 4; ++pb)
 #pragma unroll
           for (int cb = 0; cb < NCB; ++cb) acc[pb][cb] = FMX_MFMA_16x16x32(wf[cb], af[pb], acc[pb][cb]);
       }
 
-    // ---- epilogue after the last chunk: lane (l16, kg) of block (pb, cb) holds output channels cb * 16 + kg * 4 + 0..3 of pixel (row 2 * wave + (pb >> 1),
-    //      column (pb & 1) * 16 + l16) ----
+    // ---- epilogue after the last chunk, in the accumulator layout ----
     if (chunk == p.nchunks - 1) {
-      const int img = tile / tiles_per_img, tin = tile - img * tiles_per_img;
-      const int ty = tin / p.tiles_x, tx = tin - ty * p.tiles_x;
+      const TilePos t = tile_decode(tile, p.tiles_x, tiles_per_img);
 #pragma unroll
       for (int pb = 0; pb < 4; ++pb) {
-        const int oy = ty * TH + 2 * wave + (pb >> 1), ox = tx * TW + (pb & 1) * 16 + l16;
-        const bool ok = oy < oh && ox < ow;
-        const long m = ((long)img * oh + oy) * ow + ox;
+        const auto [ok, m] = out_pixel(t, wave, pb, l16, oh, ow);
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) {
-          const int col = cb * 16 + kg * 4;
+          const int col = acc_chan(cb, kg);
           f16x4 r1 = {(f16)0.0f, (f16)0.0f, (f16)0.0f, (f16)0.0f}, r2 = r1;
           if (p.res1 && ok) r1 = *reinterpret_cast<const f16x4*>(p.res1 + m * p.ld_res1 + col);
           if (p.res2 && ok) r2 = *reinterpret_cast<const f16x4*>(p.res2 + m * p.ld_res2 + col);
@@ -221,8 +205,6 @@ __global__ void esrgan_unpack_kernel(const f16* __restrict__ y, long ld, long np
   }
 }
 
-bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-
 }  // namespace
 
 extern "C" int fmx_conv3x3_dense_f16(const void* x, int64_t ld_x, int32_t n, int32_t h, int32_t w, int32_t cin, const void* wgt, const void* bias, int32_t cout,
@@ -248,18 +230,10 @@ extern "C" int fmx_conv3x3_dense_f16(const void* x, int64_t ld_x, int32_t n, int
                   "conv3x3_dense: out lies inside x: it must be a column window of the same pitch, disjoint from the input columns [0, %d)", cin);
     }
   }
-  const int tiles_x = (ow + TW - 1) / TW, tiles_y = (oh + TH - 1) / TH;
-  const long ntiles = (long)n * tiles_x * tiles_y;
-  FMX_REQUIRE(ntiles < (1L << 31), "conv3x3_dense: too many tiles for one launch (split the batch)");
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-      return fmx_set_error(FMX_E_UNSUPPORTED, "conv3x3_dense: cannot read the device's CU count");
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_dense_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_dense_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    cus = v;
-  }
+  const TileGrid g = tile_grid(n, oh, ow);
+  FMX_REQUIRE(g.one_launch(), "conv3x3_dense: too many tiles for one launch (split the batch)");
+  const unsigned grid = persistent_grid(g.ntiles);   // one persistent workgroup per CU
+  if (!grid) return fmx_set_error(FMX_E_UNSUPPORTED, "conv3x3_dense: cannot read the device's CU count");
   DenseParams p;
   p.x = (const f16*)x;
   p.wgt = (const f16*)wgt;
@@ -270,12 +244,14 @@ extern "C" int fmx_conv3x3_dense_f16(const void* x, int64_t ld_x, int32_t n, int
   p.ld_x = ld_x; p.ld_res1 = ld_res1; p.ld_res2 = ld_res2; p.ld_out = ld_out;
   p.slope = slope; p.alpha = alpha; p.beta = beta;
   p.h = h; p.w = w; p.oh = oh; p.ow = ow; p.up = up2x; p.cin = cin; p.nchunks = cin / CK;
-  p.tiles_x = tiles_x; p.tiles_y = tiles_y; p.ntiles = (int)ntiles;
-  const unsigned grid = (unsigned)(ntiles < cus ? ntiles : cus);   // one persistent workgroup per CU
-  if (cout == 32)
+  p.tiles_x = g.tiles_x; p.tiles_y = g.tiles_y; p.ntiles = (int)g.ntiles;
+  if (cout == 32) {
+    lds_ceiling_once<&conv3x3_dense_kernel<2>, SMEM>();
     hipLaunchKernelGGL(conv3x3_dense_kernel<2>, dim3(grid), dim3(256), SMEM, (hipStream_t)stream, p);
-  else
+  } else {
+    lds_ceiling_once<&conv3x3_dense_kernel<4>, SMEM>();
     hipLaunchKernelGGL(conv3x3_dense_kernel<4>, dim3(grid), dim3(256), SMEM, (hipStream_t)stream, p);
+  }
   FMX_LAUNCH_CHECK("fmx_conv3x3_dense_f16");
   return FMX_OK;
 }

@@ -13,18 +13,19 @@
 //   * the accumulator block hands lanes 0-15 the 4 output channels of one pixel each: bias, one 8-byte store per pixel, 128 contiguous bytes per block.
 // Bound: HBM (the input read once, the 1.6x halo from L2).  Wider inputs (the UNet's own `out` convolution: 320 -> 4 channels, backend/nn/unet.py:760-764) are
 // walked in channel chunks of C = 128 / 64 / 32 (the widest that divides the channel count): patch and weights of a chunk staged, 9 taps accumulated, next chunk.
-#include "fmx_common.hpp"
+// The GroupNorm + SiLU staging and the host side of the launch: fmx_conv_direct.hpp (this kernel keeps its own 4-row tile, index decode and patch geometry).
+#include "fmx_conv_direct.hpp"
 
 namespace {
 
-constexpr int TH = 4, TW = 32;            // output tile of a workgroup
-constexpr int PH = TH + 2;
+constexpr int NTH = 4;                    // output tile of a workgroup: NTH rows of TW pixels, a row per wave
+constexpr int NPH = NTH + 2;
 // staged pixels per patch row: TW + 2 halo, rounded up to whole DMA pieces (4 pixels of 128 channels, 8 of 64, 16 of 32)
 constexpr int patch_width(int c) { return (TW + 2 + 1024 / (c * 2) - 1) / (1024 / (c * 2)) * (1024 / (c * 2)); }
 
 // C: channels per chunk (staged at once); ctot: channels of the input (a multiple of C)
 // GN (round 6): the input is the UN-normalised tensor and `ss` its GroupNorm's (image, channel) {scale, shift} table (gn_finalize): the patch is staged
-// through registers -- silu(fma(x, scale, shift)) with gn_apply's own arithmetic and rounding, zeros outside the image -- instead of by LDS-DMA, and the
+// through registers -- gn_silu_octet: gn_apply's own arithmetic and rounding, zeros outside the image -- instead of by LDS-DMA, and the
 // norm_out -> swish -> conv_out tail of the VAE decoder (backend/nn/vae.py:266-271) loses its GroupNorm apply pass (one read + one write of the full-size tensor)
 template <int C, bool GN = false>
 __global__ __launch_bounds__(256, 2) void conv3x3_narrow_kernel(const f16* __restrict__ x, long x_bytes, const f16* __restrict__ wgt, const f16* __restrict__ bias,
@@ -36,7 +37,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_narrow_kernel(const f16* __res
   constexpr int CHUNKS = PIXB / 16;                 // 16-byte chunks per pixel
   constexpr int PIECES_ROW = PW / PPP;              // pieces per patch row
   static_assert(PW % PPP == 0 && CHUNKS <= 16 && (C % 32) == 0, "piece geometry");
-  constexpr int PATCH = PH * PW * PIXB;
+  constexpr int PATCH = NPH * PW * PIXB;
   constexpr int KSTEPS = C / 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const patch = smem;
@@ -49,7 +50,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_narrow_kernel(const f16* __res
   const int tx = t % tiles_x; t /= tiles_x;
   const int ty = t % tiles_y;
   const int img = t / tiles_y;
-  const int x0 = tx * TW, y0 = ty * TH;
+  const int x0 = tx * TW, y0 = ty * NTH;
 
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(x), 0, (unsigned)x_bytes, 0x00020000);
   constexpr unsigned OOB = 0xC0000000u;
@@ -61,51 +62,33 @@ __global__ __launch_bounds__(256, 2) void conv3x3_narrow_kernel(const f16* __res
     for (int i = tid; i < 4 * 9 * C / 8; i += 256) {
       const int row = i / (9 * C / 8), r8 = i - row * (9 * C / 8);
       const int tap = r8 / (C / 8), c8 = r8 - tap * (C / 8);
-      f16x8 v;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = (f16)0.0f;
+      f16x8 v = zero_octet();
       if (row < nout) v = *reinterpret_cast<const f16x8*>(wgt + ((long)row * 9 + tap) * ctot + c0 + c8 * 8);
       *reinterpret_cast<f16x8*>(wl + ((long)row * 9 + tap) * C + c8 * 8) = v;
     }
     if constexpr (GN) {
       // ---- input patch through registers: item i = (patch pixel i / CHUNKS, logical chunk i % CHUNKS); 256 % CHUNKS == 0, so a thread keeps ONE chunk ----
-      constexpr int ITEMS = PH * PW * CHUNKS, ITERS = (ITEMS + 255) / 256;
+      constexpr int ITEMS = NPH * PW * CHUNKS, ITERS = (ITEMS + 255) / 256;
       const int cc = tid % CHUNKS;
-      const float* ssp = ss + ((long)img * ctot + c0 + cc * 8) * 2;
       f32x4 sv[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) sv[i] = *reinterpret_cast<const f32x4*>(ssp + i * 4);   // {scale, shift} of channels 2i, 2i + 1
+      load_scale_shift(sv, ss + ((long)img * ctot + c0 + cc * 8) * 2);
       f16x8 v[ITERS];
-      int lo[ITERS];                                         // -1: no item; else LDS byte offset, bit 30 = outside the image
+      int lo[ITERS];
 #pragma unroll
       for (int it = 0; it < ITERS; ++it) {
         const int pi = tid / CHUNKS + it * (256 / CHUNKS);
         const int pr = pi / PW, q = pi - pr * PW;
         const int gy = y0 - 1 + pr, gx = x0 - 1 + q;
-        const bool in_patch = pi < PH * PW;
+        const bool in_patch = pi < NPH * PW;
         const bool ok = in_patch && gy >= 0 && gy < h && gx >= 0 && gx < w;
-        lo[it] = in_patch ? ((pi * PIXB + ((cc ^ (q & (CHUNKS - 1))) << 4)) | (ok ? 0 : (1 << 30))) : -1;
+        lo[it] = gn_item_off(in_patch, ok, pi * PIXB + ((cc ^ (q & (CHUNKS - 1))) << 4));
         if (ok) v[it] = *reinterpret_cast<const f16x8*>(x + (img_base + (long)gy * w + gx) * ctot + c0 + cc * 8);
       }
 #pragma unroll
-      for (int it = 0; it < ITERS; ++it) {
-        if (lo[it] < 0) continue;
-        f16x8 r;
-        if (lo[it] & (1 << 30)) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) r[e] = (f16)0.0f;
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const f32x4 sq = sv[e >> 1];
-            r[e] = (f16)silu_f(fmaf((float)v[it][e], sq[(e & 1) * 2], sq[(e & 1) * 2 + 1]));   // gn_apply_kernel's arithmetic, bit for bit
-          }
-        }
-        *reinterpret_cast<f16x8*>(patch + (lo[it] & ((1 << 30) - 1))) = r;
-      }
+      for (int it = 0; it < ITERS; ++it) gn_silu_store(patch, lo[it], v[it], sv);
     } else
     // ---- input patch -> LDS: piece p = (patch row pr, pixels pc * PPP .. + PPP); lane -> pixel lane / CHUNKS, physical chunk lane % CHUNKS ---------
-    for (int p = wave; p < PH * PIECES_ROW; p += 4) {       // uniform trip count per wave
+    for (int p = wave; p < NPH * PIECES_ROW; p += 4) {       // uniform trip count per wave
       const int pr = p / PIECES_ROW, pc = p - pr * PIECES_ROW;
       const int q = pc * PPP + lane / CHUNKS;               // patch-local pixel index in its row
       const int gy = y0 - 1 + pr, gx = x0 - 1 + q;
@@ -127,10 +110,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_narrow_kernel(const f16* __res
 #pragma unroll
         for (int ks = 0; ks < KSTEPS; ++ks) {
           f16x8 wf = *reinterpret_cast<const f16x8*>(wrow + (ky * 3 + kx) * C + ks * 32 + kg * 8);
-          if (l16 >= 4) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) wf[e] = (f16)0.0f;
-          }
+          if (l16 >= 4) wf = zero_octet();
 #pragma unroll
           for (int bl = 0; bl < 2; ++bl) {
             const int q = bl * 16 + l16 + kx;                  // patch pixel of this lane's output pixel under tap kx
@@ -169,23 +149,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_narrow_kernel(const f16* __res
 template <int C, bool GN = false>
 int launch_narrow(const void* x, long x_bytes, const void* wgt, const void* bias, void* out, int n, int h, int w, int ctot, int nout, int ld_out, hipStream_t st,
                   const float* ss = nullptr) {
-  constexpr int SMEM = PH * patch_width(C) * C * 2 + 4 * 9 * C * 2;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_narrow_kernel<C, GN>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    attr = true;
-  }
-  const int tiles_x = (w + TW - 1) / TW, tiles_y = (h + TH - 1) / TH;
-  hipLaunchKernelGGL((conv3x3_narrow_kernel<C, GN>), dim3((unsigned)(n * tiles_x * tiles_y)), dim3(256), SMEM, st, (const f16*)x, x_bytes, (const f16*)wgt, (const f16*)bias,
-                     (f16*)out, n, h, w, ctot, nout, ld_out, tiles_x, tiles_y, ss);
+  constexpr int SMEM = NPH * patch_width(C) * C * 2 + 4 * 9 * C * 2;
+  lds_ceiling_once<&conv3x3_narrow_kernel<C, GN>, SMEM>();
+  const TileGrid g = tile_grid(n, h, w, NTH);
+  hipLaunchKernelGGL((conv3x3_narrow_kernel<C, GN>), dim3((unsigned)g.ntiles), dim3(256), SMEM, st, (const f16*)x, x_bytes, (const f16*)wgt, (const f16*)bias,
+                     (f16*)out, n, h, w, ctot, nout, ld_out, g.tiles_x, g.tiles_y, ss);
   FMX_LAUNCH_CHECK("fmx_conv3x3_narrow_f16");
   return FMX_OK;
 }
 
 }  // namespace
-
-int fmx_launch_gn_finalize(const float* partial, int32_t nchunks, int32_t c, int32_t n, int32_t groups, int32_t hw, float eps, const void* gamma,
-                           const void* beta, float* scale_shift, hipStream_t st);   // fmx_norm.hip
 
 // silu(group_norm(x)) -> conv3x3 with at most 4 output channels, one launch (+ the statistics' finalize): see fmx.h
 extern "C" int fmx_conv3x3_narrow_gn_silu_f16(const void* x, int32_t n, int32_t h, int32_t w, int32_t c, const float* x_partial, int32_t x_nchunks, int32_t groups,
@@ -194,8 +167,8 @@ extern "C" int fmx_conv3x3_narrow_gn_silu_f16(const void* x, int32_t n, int32_t 
   FMX_REQUIRE(x && wgt && out && x_partial && gamma && beta && scale_shift && n > 0 && h > 0 && w > 0 && x_nchunks >= 1, "conv3x3_narrow_gn_silu: bad arguments");
   FMX_REQUIRE(nout >= 1 && nout <= 4 && ld_out >= nout, "conv3x3_narrow_gn_silu: 1..4 output channels, ld_out >= nout (got %d, %d)", nout, ld_out);
   FMX_REQUIRE(c >= 32 && (c % 32) == 0 && c <= 2048 && groups > 0 && (c % groups) == 0, "conv3x3_narrow_gn_silu: input channels must be a multiple of 32 and of the group count (got %d, %d groups)", c, groups);
-  FMX_REQUIRE(fmx_aligned16(x) && fmx_aligned16(wgt) && fmx_aligned16(scale_shift) && (ld_out != 4 || (reinterpret_cast<uintptr_t>(out) & 7u) == 0), "conv3x3_narrow_gn_silu: operands must be 16-byte aligned");
-  FMX_REQUIRE((long)n * ((w + TW - 1) / TW) * ((h + TH - 1) / TH) < (1L << 31), "conv3x3_narrow_gn_silu: too many tiles for one launch (split the batch)");
+  FMX_REQUIRE(fmx_aligned16(x) && fmx_aligned16(wgt) && fmx_aligned16(scale_shift) && (ld_out != 4 || aligned8(out)), "conv3x3_narrow_gn_silu: operands must be 16-byte aligned");
+  FMX_REQUIRE(tile_grid(n, h, w, NTH).one_launch(), "conv3x3_narrow_gn_silu: too many tiles for one launch (split the batch)");
   hipStream_t st = (hipStream_t)stream;
   const int rc = fmx_launch_gn_finalize(x_partial, x_nchunks, c, n, groups, h * w, eps, gamma, beta, scale_shift, st);
   if (rc != FMX_OK) return rc;
@@ -210,9 +183,9 @@ extern "C" int fmx_conv3x3_narrow_f16(const void* x, int32_t n, int32_t h, int32
   FMX_REQUIRE(x && wgt && out && n > 0 && h > 0 && w > 0, "conv3x3_narrow: bad arguments");
   FMX_REQUIRE(nout >= 1 && nout <= 4 && ld_out >= nout, "conv3x3_narrow: 1..4 output channels, ld_out >= nout (got %d, %d)", nout, ld_out);
   FMX_REQUIRE(c >= 32 && (c % 32) == 0 && c <= 2048, "conv3x3_narrow: input channels must be a multiple of 32, 32..2048 (got %d)", c);
-  FMX_REQUIRE(fmx_aligned16(x) && fmx_aligned16(wgt) && (ld_out != 4 || (reinterpret_cast<uintptr_t>(out) & 7u) == 0), "conv3x3_narrow: operands must be 16-byte aligned");
+  FMX_REQUIRE(fmx_aligned16(x) && fmx_aligned16(wgt) && (ld_out != 4 || aligned8(out)), "conv3x3_narrow: operands must be 16-byte aligned");
   const double bytes = (double)n * h * w * c * 2.0;
-  FMX_REQUIRE(bytes < 3.0e9 && (long)n * ((w + TW - 1) / TW) * ((h + TH - 1) / TH) < (1L << 31), "conv3x3_narrow: input beyond the 32-bit offset range of one launch (split the batch)");
+  FMX_REQUIRE(bytes < 3.0e9 && tile_grid(n, h, w, NTH).one_launch(), "conv3x3_narrow: input beyond the 32-bit offset range of one launch (split the batch)");
   hipStream_t st = (hipStream_t)stream;
   if ((c % 128) == 0) return launch_narrow<128>(x, (long)bytes, wgt, bias, out, n, h, w, c, nout, ld_out, st);
   if ((c % 64) == 0) return launch_narrow<64>(x, (long)bytes, wgt, bias, out, n, h, w, c, nout, ld_out, st);

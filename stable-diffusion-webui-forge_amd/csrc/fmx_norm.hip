@@ -5,7 +5,7 @@
 // torch.cat of the skip tensor in front of it (:741); and F.layer_norm (backend/operations.py:327).
 #include <stdlib.h>
 
-#include "fmx_common.hpp"
+#include "fmx_conv_direct.hpp"   // gn_norm_f: the fused convolutions stage what gn_apply_kernel stores
 
 namespace {
 
@@ -266,9 +266,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const f16* __restrict__ x
         f16x8 r;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          float f = fmaf((float)v[u][e], e < 4 ? sc0[e & 3] : sc1[e & 3], e < 4 ? sh0[e & 3] : sh1[e & 3]);
-          if (SILU) f = silu_f(f);
-          r[e] = (f16)f;
+          r[e] = (f16)gn_norm_f<SILU>((float)v[u][e], e < 4 ? sc0[e & 3] : sc1[e & 3], e < 4 ? sh0[e & 3] : sh1[e & 3]);
         }
         *reinterpret_cast<f16x8*>(y + (ibase + pxs[u]) * C + ch) = r;
       }

@@ -21,6 +21,7 @@ from forge_amd import hipops as ops  # noqa: E402
 
 import kernel_refs as R  # noqa: E402
 from test_gpu_gemm_windows import Win, changed_outside, gen, rnd, sentinel_buffer  # noqa: E402
+from test_gpu_taesd import WALK_SHAPE, assert_tiles_exceed_cus, case_id  # noqa: E402
 
 DEV = "cuda"
 H16 = torch.float16
@@ -70,6 +71,8 @@ def run_dense(shape, cin, cout, epi, up=False):
     k = dense_case(shape, cin, cout, up)
     n, h, w = shape
     m = k["m"]
+    if shape == WALK_SHAPE:
+        assert_tiles_exceed_cus(n, h << up, w << up)
     x = x_window(k["x"], n, h, w, cin)
     wk = Win(tap_major(k["wt"]), 1, 2).on(DEV)
     b = Win(k["bias"], left=8, right=8).on(DEV)
@@ -89,10 +92,12 @@ def run_dense(shape, cin, cout, epi, up=False):
     assert e <= 1.0, f"{what}: error {e:.3g}x CONV_TOL"
 
 
-@pytest.mark.parametrize("epi", list(EPILOGUES))
-@pytest.mark.parametrize("cout", COUTS)
-@pytest.mark.parametrize("cin", CINS)
-@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+# the last two: the tile walk (see WALK_SHAPE) across the wrap from a tile's last channel chunk to chunk 0 of the workgroup's next tile, at both widths
+DENSE_CASES = [(s, ci, co, e) for e in EPILOGUES for co in COUTS for ci in CINS for s in SHAPES] + [(WALK_SHAPE, 96, 32, "res1_res2"),
+                                                                                                 (WALK_SHAPE, 192, 64, "res1_res2")]
+
+
+@pytest.mark.parametrize("shape,cin,cout,epi", DENSE_CASES, ids=[case_id(*c) for c in DENSE_CASES])
 def test_conv3x3_dense(shape, cin, cout, epi):
     run_dense(shape, cin, cout, epi)
 

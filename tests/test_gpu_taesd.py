@@ -7,6 +7,7 @@ Kernel level follows tests/test_gpu_vae_direct.py: sentinel-filled oversize dest
 inputs as ROW windows of buffers holding 30000 around them (so image 0's top border and the last image's bottom border have 30000 next to them in
 memory where the kernel must see zeros; n = 2 shows a halo read into the neighbouring image), references in fp64 on the rounded inputs, tolerance
 kernel_refs.CONV_TOL (same arithmetic: fp32 accumulation over K = 576, fp32 epilogue adds, one rounding).  The kernel's tile is 8 x 32 output pixels."""
+import ctypes as C
 import math
 from functools import lru_cache
 
@@ -29,6 +30,9 @@ SHAPES = [(2, 5, 7), (2, 9, 33), (1, 16, 64)]
 # with up2x: 10 x 14 (sub-tile) and 10 x 34 (one past the tile in both directions of the OUTPUT)
 UP_SHAPES = [(2, 5, 7), (1, 5, 17)]
 VARIANTS = ("bias", "bias_relu", "bias_residual_relu")
+# 2 x 5 x 33 = 330 tiles, ragged in both directions: more tiles than the device has CUs, so persistent workgroups walk on to a SECOND tile (some of them:
+# the others take one), staged into the other LDS buffer under the first one's MFMA loop, and the second tiles lie in the other image
+WALK_SHAPE = (2, 37, 1050)
 
 
 def tap_major(wt):
@@ -53,10 +57,21 @@ def c64_ref(shape, dtype, up, bias, residual, relu):
     return torch.relu(y) if relu else y
 
 
+def assert_tiles_exceed_cus(n, oh, ow):
+    """the tile walk of a persistent kernel is covered only while a launch has more 8 x 32 tiles than the device has CUs"""
+    from forge_amd import _lib
+    cus = C.c_int(0)
+    _lib.check(_lib.lib().fmx_device_info(C.byref(cus), None, None, 0), "fmx_device_info")
+    tiles = n * ((oh + 7) // 8) * ((ow + 31) // 32)
+    assert tiles > cus.value > 0, f"{tiles} tiles on {cus.value} CUs: no workgroup walks to a second tile"
+
+
 def run_c64(shape, dtype, up, bias, residual, relu, what):
     k = c64_case(shape, dtype, up)
     n, h, w = shape
     m = k["m"]
+    if shape == WALK_SHAPE:
+        assert_tiles_exceed_cus(n, h << up, w << up)
     x = Win(k["x"].reshape(n * h * w, 64), 2, 3).on(DEV).view(n, h, w, 64)
     wk = Win(tap_major(k["wt"]), 1, 2).on(DEV)
     b = Win(k["bias"], left=8, right=8).on(DEV) if bias else None
@@ -74,9 +89,14 @@ def run_c64(shape, dtype, up, bias, residual, relu, what):
     assert e <= 1.0, f"{what}: error {e:.3g}x CONV_TOL"
 
 
-@pytest.mark.parametrize("dt", list(DTYPES))
-@pytest.mark.parametrize("variant", VARIANTS)
-@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+def case_id(*parts):
+    return "-".join("x".join(map(str, p)) if isinstance(p, tuple) else str(p) for p in parts)
+
+
+C64_CASES = [(s, v, d) for d in DTYPES for v in VARIANTS for s in SHAPES] + [(WALK_SHAPE, "bias_residual_relu", d) for d in DTYPES]
+
+
+@pytest.mark.parametrize("shape,variant,dt", C64_CASES, ids=[case_id(*c) for c in C64_CASES])
 def test_conv3x3_c64(shape, variant, dt):
     run_c64(shape, DTYPES[dt], False, True, "residual" in variant, "relu" in variant, f"conv3x3_c64 {shape} {variant} {dt}")
 
