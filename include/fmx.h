@@ -269,9 +269,10 @@ int fmx_softmax_rows_f16(void* x, int64_t nrows, int32_t ncols, int64_t ld, void
 /* ------------------------------------------------------------------------------------------------
  * GroupNorm over NHWC fp16 (optionally the channel-concat of two tensors), fp32 statistics, 1 read + 1 write.
  *   statistics : partial[n][chunk][c][2] fp32 = {sum x, sum x^2} of channel c over the chunk's pixels of image n.  Produced EITHER by the
- *                convolution / linear that wrote the tensor -- fmx_gemm_conv_stats_f16 below emits one chunk per 256-row output tile from
- *                its epilogue, so the tensor is never re-read for statistics -- OR by fmx_groupnorm_stats_f16 (any nchunks <= 1024; one
- *                source tensor [n][hw][c] with pixel stride ld).  A partial buffer is read-only for apply: a tensor that feeds two
+ *                convolution / linear that wrote the tensor -- fmx_gemm_conv_stats_f16 below emits one chunk per 128-, 256- or 512-row output
+ *                tile from its epilogue, so the tensor is never re-read for statistics -- OR by fmx_groupnorm_stats_f16 (any nchunks <= 1024; one
+ *                source tensor [n][hw][c] with pixel stride ld; chunk k = pixels [k * per, (k + 1) * per), per = ceil(hw / nchunks), and a chunk
+ *                that starts behind the image is written as {0, 0}).  A partial buffer is read-only for apply: a tensor that feeds two
  *                GroupNorms (a UNet skip connection) keeps its statistics.
  *   apply      : folds the chunks of both sources into per-channel {scale, shift} (scale_shift: fp32 workspace [n][c0+c1][2], fixed
  *                summation order -> deterministic), then y = x * scale[c] + shift[c] = (x - mean_g) * rstd_g * gamma[c] + beta[c],
@@ -284,10 +285,16 @@ int fmx_groupnorm_apply_f16(const void* x0, const void* x1, int32_t c0, int32_t 
                             const void* gamma, const void* beta, int32_t silu, float* scale_shift, void* y, void* stream);
 
 /* fmx_gemm_conv_f16 that ALSO leaves the GroupNorm statistics of its fp16 output [M = n*oh*ow][nout] (ld_out == nout, no GEGLU) in
- * partial[n][chunks][nout][2]: from the epilogue of the 256-row tiles when an image is a whole number of them (oh*ow % 256 == 0) and the
- * tile choice is a 256-row kernel, else by a statistics pass launched behind the GEMM -- the caller cannot tell the difference except by
- * *chunks_out (host): the chunk count it must hand to fmx_groupnorm_apply_f16.  partial must hold n * max_chunks * nout * 2 floats,
- * max_chunks >= max(oh*ow / 256, fallback_chunks); fallback_chunks (1..1024) is the chunk count of the separate pass. */
+ * partial[n][chunks][nout][2]: from the GEMM's own epilogue, one chunk per output tile of `rows` rows (chunk k of an image = its output rows
+ * [k * rows, (k + 1) * rows)), when the tile choice emits statistics and an image is a whole number of tiles (oh*ow % rows == 0).  rows follows
+ * the tile: 128 for the 128-row 4-wave tiles (128x128 and 128x64, two-stage and ring, with or without split-K, and the 128x160 ring tile),
+ * 256 for the 256x256 and 256x320 tiles, 512 for the 512x128 tile; the other tiles (64x64, the two-stage 128x160, 320x256, 64x160, 160x64) emit
+ * none.  Otherwise a statistics pass (fmx_groupnorm_stats_f16 with fallback_chunks chunks) is launched behind the GEMM -- the caller cannot
+ * tell the difference except by *chunks_out (host): the chunk count it must hand to fmx_groupnorm_apply_f16.  partial must hold
+ * n * max_chunks * nout * 2 floats, max_chunks >= fallback_chunks; fallback_chunks (1..1024) is the chunk count of the separate pass.  A
+ * max_chunks below oh*ow / rows is not an error: when oh*ow / rows > max_chunks the launch silently falls back to the pass behind the GEMM
+ * (a caller that wants the epilogue route on every tile passes max_chunks >= max(oh*ow / 128, fallback_chunks)).  Exactly the first
+ * n * *chunks_out * nout * 2 floats of partial are written. */
 int fmx_gemm_conv_stats_f16(const fmx_gemm_args* args /* host */, float* partial, int32_t max_chunks, int32_t fallback_chunks,
                             int32_t* chunks_out /* host */, void* stream);
 

@@ -1,5 +1,5 @@
 """fp64 references and ulp tolerances shared by the kernel-level parity tests (tests/test_gpu_kernels_bf16.py, tests/test_gpu_small_kernels.py,
-tests/test_gpu_gemm_windows.py, tests/test_gpu_vae_direct.py, tests/test_gpu_sampler_kernels.py) and their CPU companion (tests/test_kernel_ref_teeth.py), which plants one plausible bug into each reference and checks that the GPU tests'
+tests/test_gpu_gemm_windows.py, tests/test_gpu_vae_direct.py, tests/test_gpu_sampler_kernels.py, tests/test_gpu_groupnorm_routes.py) and their CPU companion (tests/test_kernel_ref_teeth.py), which plants one plausible bug into each reference and checks that the GPU tests'
 tolerance would reject it.
 
 Discipline: every reference is the same operation in fp64 on the kernel's own rounded inputs (the fp16 / bf16 tensors it read, upcast).
@@ -832,3 +832,131 @@ def philox_raw_ref(seed, offset, n, plant=None):
     k1 = z if plant == "seed_hi_ignored" else np.full(n, (seed >> 32) & 0xFFFFFFFF, dtype=np.uint32)
     c = (z, off, idx, z) if plant == "offset_in_word1" else (off, z, idx, z)
     return np.stack(philox4x32_10(*c, k0, k1), 1)
+
+
+# ---- the GroupNorm statistics chain (tests/test_gpu_groupnorm_routes.py) --------------------------------------------------------------------------
+# Producer records (fmx_gemm_conv_stats from every tile's epilogue or the pass behind the GEMM), the stand-alone pass (fmx_groupnorm_stats) and both folds
+# of fmx_groupnorm_apply.  Records are held PER CHUNK to the statistics tolerance the other files use on sums over chunks (rtol 2e-5, atol 2e-3:
+# test_gpu_vae_direct.STAT_TOL, unchanged): a chunk is at most 512 fp32 additions of values |x| ~ 1, relative ~1e-6.  GroupNorm outputs: GN_TOL as it stands.
+#
+# The {scale, shift} table of the separate fold (gn_finalize_kernel) is the only fp32 result of the chain that a test can read.  Its unit: relative to
+# |scale| for scale = rstd gamma, and to |beta| + |mean scale| (the summed magnitudes) for shift = beta - mean scale.  The tolerance is not derived but
+# MEASURED, as the worst such error of gn_fold_emul2 (fp32 chunk sums, the fold in double, mean / rstd / scale / shift in fp32: the kernel's formula in plain
+# torch) against fp64 over every separate-fold case of the GPU file in both element types, on the CPU:  1.96e-7 (fp16) / 1.86e-7 (bf16), recorded as 2.0e-7
+# (a handful of fp32 roundings of 6e-8 each between the variance and the shift).  Four times that is allowed; tests/test_kernel_ref_teeth.py asserts that the
+# emulation stays at or below the recorded figure.
+GN_TABLE_EMUL = 2.0e-7
+GN_TABLE_TOL = 4 * GN_TABLE_EMUL
+#
+# Worst excess (units of the tolerance) per part: the emulations below on the GPU file's inputs (tests/test_kernel_ref_teeth.py asserts <= 1 and prints
+# them) and the worst `MEASURED` line of the GPU file on MI355X, fp16 / bf16:
+#   part                                   emulation        MI355X
+#   producer output vs CONV_TOL (1, 2)     -                0.400 / 0.400
+#   producer records per chunk (1, 2)      0.010 / 0.010    0.009 / 0.007   (split-K: 0.006 / 0.006)
+#   stand-alone pass per chunk (3)         0.013 / 0.009    0.040 / 0.048
+#   GroupNorm output, fused fold (4)       0.390 / 0.381    0.390 / 0.381
+#   GroupNorm output, separate fold (4)    0.400 / 0.400    0.400 / 0.400
+#   scale / shift table (4)                0.245 / 0.233    0.213 / 0.231
+# (The statistics tolerance is two decades above what either the emulation or the kernels need: what it resolves is a record that is wrong -- a missing or
+# misplaced chunk is thousands of tolerances -- not the summation order.  The stand-alone pass adds its pixels in sequence where torch adds pairwise: 4x the
+# emulation's error, still 1/20 of the tolerance.)  Of the 655 cases of the GPU file 30 are skipped, each a dispatcher refusal of a forced tile that the test
+# first reproduces by its FMX_REQUIRE text: tile id 10 (no output statistics: 26 cases) and tile id 9 with upsample-on-load (4 cases).
+
+
+def stat_excess(got, want, rtol, atol):
+    """torch.testing.assert_close's criterion as a figure: max |got - want| / (atol + rtol |want|), <= 1 passes; a non-finite record is infinitely wrong"""
+    got, want = got.double().cpu(), want.double().cpu()
+    return float(((got - want).abs() / (atol + rtol * want.abs())).nan_to_num(nan=math.inf).max())
+
+
+def _chunked(o, nchunks):
+    """[n, hw, c] -> [n, nchunks, per, c], per = ceil(hw / nchunks) consecutive pixels per chunk, zero rows behind pixel hw (chunks past the image are empty)"""
+    n, hw, c = o.shape
+    per = -(-hw // nchunks)
+    return F.pad(o, (0, 0, 0, nchunks * per - hw)).view(n, nchunks, per, c)
+
+
+def chunk_sums_ref(out, n, nchunks):
+    """fp64 {sum, sum of squares} per (image, chunk, channel) of the stored tensor [n * hw, c] (or [n, hw, c]) -> [n, nchunks, c, 2].  Chunk k of an image is
+    pixels [k per, (k + 1) per), per = ceil(hw / nchunks): the rows of the k-th 128 / 256 / 512-row tile of the image for the GEMM epilogues (hw = nchunks *
+    rows), the block's pixels for the statistics pass (csrc/fmx_norm.hip gn_stats_kernel); a chunk that starts behind the image is {0, 0}"""
+    o = _chunked(out.double().reshape(n, -1, out.shape[-1]), nchunks)
+    return torch.stack([o.sum(2), (o * o).sum(2)], -1)
+
+
+def chunk_sums_emul(out, n, nchunks, plant=None):
+    """the same records from fp32 sums (torch's summation order, not the kernels').  plant: None or one bug -- "last_chunk_dropped" (the last chunk of every image
+    never written: a zeroed buffer keeps {0, 0}), "next_image_slot" (image i's records in image i + 1's slots, cyclically), "empty_chunk_stale" (chunks behind
+    the image are not written and keep an earlier launch's record, here chunk 0's)"""
+    o = _chunked(out.float().reshape(n, -1, out.shape[-1]), nchunks)
+    hw = out.numel() // (n * out.shape[-1])
+    p = torch.stack([o.sum(2), (o * o).sum(2)], -1)
+    if plant == "last_chunk_dropped":
+        p[:, -1] = 0.0
+    elif plant == "next_image_slot":
+        p = p.roll(1, 0)
+    elif plant == "empty_chunk_stale":
+        first_empty = -(-hw // -(-hw // nchunks))
+        p[:, first_empty:] = p[:, :1]
+    else:
+        assert plant is None, plant
+    return p
+
+
+def gn_table_ref(x, gamma, beta, eps, groups):
+    """fp64 {scale, shift} = {rstd gamma, beta - mean rstd gamma} per (image, channel) of x [n, hw, C] -> (table [n, C, 2], magnitudes [n, C, 2] =
+    {|scale|, |beta| + |mean scale|}: the units of GN_TABLE_TOL)"""
+    n, hw, c = x.shape
+    cpg = c // groups
+    xg = x.double().view(n, hw, groups, cpg)
+    mean = xg.mean((1, 3))
+    var = (xg * xg).mean((1, 3)) - mean * mean
+    rstd = 1.0 / torch.sqrt(var.clamp_min(0.0) + eps)
+    sc = rstd.repeat_interleave(cpg, 1) * gamma.double()
+    ms = mean.repeat_interleave(cpg, 1) * sc
+    return torch.stack([sc, beta.double() - ms], -1), torch.stack([sc.abs(), beta.double().abs() + ms.abs()], -1)
+
+
+def gn_table_excess(got, x, gamma, beta, eps, groups, tol=GN_TABLE_TOL):
+    want, mag = gn_table_ref(x, gamma, beta, eps, groups)
+    return excess_abs(got, want, tol * mag)
+
+
+def gn_fold_emul2(srcs, nchs, gamma, beta, eps, groups, fused, plant=None):
+    """the table as fmx_groupnorm_apply folds it from the chunk records of one or two sources (csrc/fmx_norm.hip): fp32 records per chunk (chunk_sums_emul),
+    their sum per channel in double (`fused`, the fold inside gn_apply_kernel: each channel's sum rounded to fp32 before the group sum; else gn_finalize_kernel:
+    double throughout), group mean and variance in double, mean and rstd in fp32, scale = rstd gamma and shift = beta - mean scale in fp32.
+    srcs: [x0 [n, hw, c0]] or [x0, x1]; nchs: their chunk counts.  -> fp32 [n, C, 2].  plant: None or one bug -- "nch1_as_nch0" (source 1's records addressed with
+    source 0's chunk count: wrong strides, reads running into the next image's records), "straddle_off_by_one" (the group that straddles the two sources
+    loses source 0's last channel), "eps_1e5" (eps 1e-5 whatever the caller passed)"""
+    n, hw = srcs[0].shape[:2]
+    sums = []
+    for i, (x, nch) in enumerate(zip(srcs, nchs)):
+        p = chunk_sums_emul(x, n, nch)                                  # [n, nch, c, 2]
+        if plant == "nch1_as_nch0" and i == 1:
+            c, wrong = x.shape[-1], nchs[0]
+            flat = p.reshape(-1)
+            idx = ((torch.arange(n)[:, None, None] * wrong + torch.arange(wrong)[None, :, None]) * c + torch.arange(c)[None, None, :]) * 2
+            p = torch.stack([flat[idx % flat.numel()], flat[(idx + 1) % flat.numel()]], -1)
+        sums.append(p.double().sum(1))
+    s = torch.cat(sums, 1)                                              # [n, C, 2]
+    if plant == "straddle_off_by_one":
+        s = s.clone()
+        s[:, srcs[0].shape[-1] - 1] = 0.0
+    if fused:
+        s = s.float().double()
+    c = s.shape[1]
+    cpg = c // groups
+    g = s.view(n, groups, cpg, 2).sum(2) / float(cpg * hw)
+    mean_d = g[..., 0]
+    var = (g[..., 1] - mean_d * mean_d).clamp_min(0.0).float()
+    mean = mean_d.float()
+    rstd = torch.rsqrt(var + torch.tensor(1e-5 if plant == "eps_1e5" else eps, dtype=torch.float32))
+    sc = rstd.repeat_interleave(cpg, 1) * gamma.float()
+    return torch.stack([sc, beta.float() - mean.repeat_interleave(cpg, 1) * sc], -1)
+
+
+def gn_apply_emul(x, table, silu, dtype):
+    """y = x scale + shift (+ SiLU) in fp32, rounded once: x [n, hw, C] -> the same shape in `dtype`"""
+    y = x.float() * table[:, None, :, 0] + table[:, None, :, 1]
+    return (y * torch.sigmoid(y) if silu else y).to(dtype)

@@ -1,5 +1,5 @@
 """CPU: the kernel-level GPU tests have teeth.  For each test in tests/test_gpu_kernels_bf16.py, tests/test_gpu_small_kernels.py, each test
-family of tests/test_gpu_attention_generic.py, each window case of tests/test_gpu_gemm_windows.py, each check of tests/test_gpu_vae_direct.py and each kernel of tests/test_gpu_sampler_kernels.py, one
+family of tests/test_gpu_attention_generic.py, each window case of tests/test_gpu_gemm_windows.py, each check of tests/test_gpu_vae_direct.py, each kernel of tests/test_gpu_sampler_kernels.py and each part of tests/test_gpu_groupnorm_routes.py, one
 plausible subtle bug is planted into the fp64 reference (tests/kernel_refs.py) and evaluated on that test's own inputs; the planted result must
 lie outside the GPU test's tolerance by at least 4x (kernel_refs.excess >= 4), or -- for the exact tests -- differ in at least 4 places.
 Runs without a GPU, so a tolerance too loose to catch anything fails before anyone gets a GPU."""
@@ -1055,3 +1055,144 @@ def test_sampler_philox_planted_bugs_are_caught():
     inv = np.float32(2.3283064e-10)
     u, v = raw[:, 0] * inv + inv / 2, raw[:, 1] * np.float32(2.3283064e-10 * 6.2831855) + np.float32(2.3283064e-10 * 6.2831855) / 2
     np.testing.assert_allclose(np.sqrt(-2.0 * np.log(u)) * np.sin(v), philox_randn(K.PHILOX_SEEDS[0], 7, 257), rtol=0, atol=1e-6)
+
+
+# ---- the GroupNorm statistics chain (tests/test_gpu_groupnorm_routes.py) --------------------------------------------------------------------------
+# kernel_refs.chunk_sums_emul (fp32 records per chunk) and gn_fold_emul2 / gn_apply_emul (both folds of fmx_groupnorm_apply in plain torch) run on the GPU
+# file's own inputs: unplanted they stay inside the GPU file's tolerances (worst excess printed: the table in kernel_refs.py), with one bug planted they
+# leave them by >= 4x.
+import test_gpu_groupnorm_routes as N  # noqa: E402
+
+_DT_NAME = {H16: "f16", BF: "bf16"}
+
+
+def _stat_bites(planted, want, what):
+    e = R.stat_excess(planted, want, **N.STAT_TOL)
+    assert e >= TEETH, f"{what}: the planted bug is only {e:.3g}x the statistics tolerance"
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_gn_routes_producer_chunking_emulation_and_planted_bugs(dtype):
+    """every producer case at every chunk count its routes can report: fp32 records per chunk stay inside STAT_TOL; the last 128-row chunk dropped, and a
+    chunk in the next image's slot, are caught per chunk AND in the sum over chunks"""
+    worst = 0.0
+    for form, nout, tall, dt in N.PRODUCER_CASES:
+        if N.DTYPES[dt] != dtype:
+            continue
+        k = N.producer_case(form, dtype, nout, tall)
+        stored = N.producer_ref(form, dtype, nout, tall).to(dtype)
+        assert N.expected_chunks(1, k.n, k.hw) == [k.hw // 128] and N.expected_chunks(3, k.n, k.hw) == [N.ops._gn_chunks(k.n, k.hw)]
+        for nch in N.expected_chunks(0, k.n, k.hw):
+            worst = max(worst, R.stat_excess(R.chunk_sums_emul(stored, k.n, nch), R.chunk_sums_ref(stored, k.n, nch), **N.STAT_TOL))
+        nch = k.hw // 128
+        want = R.chunk_sums_ref(stored, k.n, nch)
+        for plant in ("last_chunk_dropped", "next_image_slot"):
+            planted = R.chunk_sums_emul(stored, k.n, nch, plant)
+            _stat_bites(planted, want, f"{N.case_id(form, nout, tall, dt)} {plant}, per chunk")
+            _stat_bites(planted.sum(1), want.sum(1), f"{N.case_id(form, nout, tall, dt)} {plant}, summed over chunks")
+    print(f"EMULATION gn producer records {dtype}: {worst:.3f}")
+    assert worst <= 1.0
+
+
+def test_gn_routes_expected_chunks_table():
+    """the route table of the GPU file at its two image sizes: 128-row tiles hw / 128, 256-row tiles hw / 256, the 512-row tile hw / 512 where it divides, the
+    fallback count elsewhere -- and every epilogue count differs from the fallback count, so the chunk count does identify the route"""
+    for hw, fb in ((256, 8), (512, 16)):
+        assert N.ops._gn_chunks(N.N_IMG, hw) == fb
+        for tile in N.TILES:
+            want = hw // 128 if tile in (1, 2, 11, 12, 13) else hw // 256 if tile in (6, 7) else 1 if tile == 9 and hw == 512 else fb
+            if tile:
+                assert N.expected_chunks(tile, N.N_IMG, hw) == [want]
+        assert fb not in (hw // 128, hw // 256, hw // 512) and set(N.expected_chunks(0, N.N_IMG, hw)) == {fb, hw // 128, hw // 256} | ({1} if hw == 512 else set())
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_gn_routes_stats_pass_emulation_and_stale_empty_chunks(dtype):
+    """fp32 records of the stand-alone pass on every case stay inside STAT_TOL; a chunk behind the image that keeps an earlier record is caught (the GPU test
+    asks for exact zeros there; the tolerance alone sees it too)"""
+    worst = 0.0
+    for c, hw, nch in N.STATS_CASES:
+        x = N.stats_case(c, hw, dtype).values
+        want = R.chunk_sums_ref(x, N.STATS_N, nch)
+        worst = max(worst, R.stat_excess(R.chunk_sums_emul(x, N.STATS_N, nch), want, **N.STAT_TOL))
+        per = -(-hw // nch)
+        if -(-hw // per) < nch:
+            planted = R.chunk_sums_emul(x, N.STATS_N, nch, "empty_chunk_stale")
+            assert bool(planted[:, -(-hw // per):].any()) and not bool(want[:, -(-hw // per):].any())
+            _stat_bites(planted, want, f"c {c} hw {hw} nchunks {nch} stale empty chunk")
+    print(f"EMULATION gn stand-alone pass records {dtype}: {worst:.3f}")
+    assert worst <= 1.0
+
+
+def _apply_all(dtype):
+    for name, hw in N.APPLY_IDS:
+        for eps in (1e-5, 1e-6):
+            yield name, hw, eps, N.apply_case(name, hw, dtype)
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_gn_routes_fold_emulations_meet_the_tolerances(dtype):
+    """both folds in plain torch on every case of the GPU file: the output inside GN_TOL, the separate fold's table at or below the MEASURED figure
+    kernel_refs.GN_TABLE_EMUL, a quarter of the tolerance (printed: the worst relative error, the figure recorded beside the constant)"""
+    worst = {"fused fold": 0.0, "separate fold": 0.0, "table": 0.0}
+    for name, hw, eps, k in _apply_all(dtype):
+        srcs, nchs = N.apply_sources(k)
+        fused, groups = k.cfg["fused"], k.cfg["groups"]
+        assert N.apply_fuses(k.cfg, k.n, hw) == fused
+        table = R.gn_fold_emul2(srcs, nchs, k.gamma.values, k.beta.values, R.f32(eps), groups, fused)
+        if not fused:
+            worst["table"] = max(worst["table"], R.gn_table_excess(table, k.x.view(k.n, hw, k.c), k.gamma.values, k.beta.values, R.f32(eps), groups, tol=1.0))
+        for silu in (False, True):
+            y = R.gn_apply_emul(k.x.view(k.n, hw, k.c), table, silu, dtype).reshape(k.n * hw, k.c)
+            key = "fused fold" if fused else "separate fold"
+            worst[key] = max(worst[key], R.excess(y, N.apply_ref(name, hw, dtype, eps, silu), dtype, *R.GN_TOL[dtype]))
+    print(f"EMULATION gn output, fused fold {dtype}: {worst['fused fold']:.3f}")
+    print(f"EMULATION gn output, separate fold {dtype}: {worst['separate fold']:.3f}")
+    print(f"EMULATION gn scale/shift table {dtype}: worst relative error {worst['table']:.3g} = {worst['table'] / R.GN_TABLE_TOL:.3f}x GN_TABLE_TOL")
+    assert worst["fused fold"] <= 1.0 and worst["separate fold"] <= 1.0
+    assert worst["table"] <= R.GN_TABLE_EMUL and R.GN_TABLE_TOL == 4 * R.GN_TABLE_EMUL
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_gn_routes_fold_planted_bugs_are_caught(dtype):
+    """source 1 folded with source 0's chunk count (the cases whose counts differ); the straddling group losing source 0's last channel; eps 1e-5 used for
+    1e-6 -- each >= 4x GN_TOL on the output of every case it applies to, and >= 4x GN_TABLE_TOL on the table where the separate fold runs"""
+    for name, hw, eps, k in _apply_all(dtype):
+        srcs, nchs = N.apply_sources(k)
+        fused, groups, c0 = k.cfg["fused"], k.cfg["groups"], k.cfg["c0"]
+        plants = []
+        if len(srcs) == 2 and nchs[0] != nchs[1] and hw >= nchs[1]:     # (one pixel in three chunks: the records that the wrong stride reaches are the empty ones)
+            plants.append("nch1_as_nch0")
+        if len(srcs) == 2 and c0 % (k.c // groups) != 0:
+            plants.append("straddle_off_by_one")
+        if eps == 1e-6:
+            plants.append("eps_1e5")
+        for plant in plants:
+            table = R.gn_fold_emul2(srcs, nchs, k.gamma.values, k.beta.values, R.f32(eps), groups, fused, plant)
+            for silu in (False, True):
+                y = R.gn_apply_emul(k.x.view(k.n, hw, k.c), table, silu, dtype).reshape(k.n * hw, k.c)
+                bites(y, N.apply_ref(name, hw, dtype, eps, silu), dtype, R.GN_TOL[dtype], f"{name} hw {hw} eps {eps} silu {silu} {plant}")
+            if not fused:
+                e = R.gn_table_excess(table, k.x.view(k.n, hw, k.c), k.gamma.values, k.beta.values, R.f32(eps), groups)
+                assert e >= TEETH, f"{name} hw {hw} eps {eps} {plant}: the planted table is only {e:.3g}x GN_TABLE_TOL"
+
+
+def test_gn_routes_case_list_reaches_both_folds_and_every_lane_layout():
+    """conditions of the GPU file: both folds are reached, for both reasons the launcher has for the separate one; a group straddles the sources in a fused and
+    in a separate case; the stand-alone pass sees idle threads, one lane per octet and a second octet block, and chunk counts beyond the pixel count"""
+    fused = {name: cfg["fused"] for name, cfg in N.APPLY_CASES.items()}
+    assert sorted(fused.values()) == [False, False, True, True]
+    for name, cfg in N.APPLY_CASES.items():
+        for hw in cfg["hws"]:
+            assert N.apply_fuses(cfg, N.APPLY_N, hw) == cfg["fused"]
+        c = cfg["c0"] + cfg["c1"]
+        ppb = -(-8192 // c)
+        assert 1 in cfg["hws"] and any(hw > ppb and hw % ppb for hw in cfg["hws"])
+    assert N.APPLY_CASES["separate_records"]["groups"] == 32 and N.APPLY_CASES["separate_groups"]["groups"] != 32
+    assert N.APPLY_CASES["fused_wide"]["c0"] // 8 > 256
+    for name in ("fused_straddle", "separate_groups"):
+        cfg = N.APPLY_CASES[name]
+        assert cfg["c0"] % ((cfg["c0"] + cfg["c1"]) // cfg["groups"]) != 0 and cfg["nch0"] != cfg["nch1"]
+    octs = [c // 8 for c in N.STATS_C]
+    assert any(o < 256 and 256 % o for o in octs) and 256 in octs and any(o > 256 for o in octs) and 1 in octs
+    assert all(any(nch > hw for c, h, nch in N.STATS_CASES if h == hw) for hw in N.STATS_HW)
