@@ -862,8 +862,7 @@ class IntegratedUNet2DConditionModel:
         h = modify(h, "before")
         oc = lay.out_channels
         wrapped = to is not None and to.get("group_norm_wrapper") is not None
-        if (not wrapped and oc <= 4 and h.dim() == 4 and h.is_contiguous() and h.shape[-1] % 32 == 0 and ops._CONV_GN_FUSE and ops._attached_stats(h) is not None
-                and h.shape[0] * h.shape[1] * h.shape[2] >= (1 << 16)):
+        if not wrapped and ops.conv3x3_narrow_gn_silu_eligible(h, oc):
             # out.0 -> SiLU -> out.2 (unet.py:755-764) in one launch: the normalisation applied while the direct kernel stages its patch (round 6)
             out = ops.conv3x3_narrow_gn_silu(h, *self.w["out.gn"], 1e-5, self.w["out.conv"][0], self.w["out.conv"][1], oc, ld_out=oc)
             self._tap("out.2", out.view(bu, hh, ww, -1)[..., :oc])

@@ -327,7 +327,7 @@ class IntegratedAutoencoderKL:
                 self._tap(up, h)
         co, cin = lay.out_channels, h.shape[-1]
         nb, oh, ow = h.shape[0], h.shape[1], h.shape[2]
-        if co <= 4 and cin % 32 == 0 and ops._CONV_GN_FUSE and ops._attached_stats(h) is not None and nb * oh * ow >= (1 << 16):
+        if ops.conv3x3_narrow_gn_silu_eligible(h, co):
             # norm_out -> swish -> conv_out in ONE launch (round 6): the normalisation applied while the direct kernel stages its input patch, the
             # GroupNorm apply pass (one read + one write of the full-resolution tensor) gone; same values, same rounding sites
             y = ops.conv3x3_narrow_gn_silu(h, *self.w["norm_out"], 1e-6, self.w["conv_out"][0], self.w["conv_out"][1], co)

@@ -7,14 +7,14 @@ Temporary / output buffers come from the active `Arena` (runtime.py) when one is
 forward allocates nothing from HIP and can be captured into a HIP graph.
 """
 import ctypes as C
-import os
+import math
 
 import torch
 
 from . import _lib
 from ._lib import AttnArgs, ConvGnArgs, GemmArgs
 
-ACT_NONE, ACT_GEGLU, ACT_GELU_TANH = 0, 1, 2
+ACT_NONE, ACT_GEGLU, ACT_GELU_TANH = (_lib.CONSTANTS["FMX_ACT_" + _n] for _n in ("NONE", "GEGLU", "GELU_TANH"))
 
 _zero_pages = {}
 _alloc = None  # callable(shape, dtype) -> tensor ; set by runtime.Arena
@@ -107,6 +107,19 @@ def stream_ptr():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _call(name, *args):
+    """One C-ABI call on torch's current stream: every compute entry point of include/fmx.h takes the stream last.  A non-zero code raises FmxError."""
+    _lib.check(getattr(_lib.lib(), name)(*args, stream_ptr()), name)
+
+
+def _timed(kind, flops, run, tag=None, nbytes=0.0):
+    """run(), between the events of the installed KernelProfiler if there is one (bench.py keys its roofline families on kind and tag)"""
+    if _profiler is not None:
+        _profiler.launch(kind, flops, run, tag=tag, nbytes=nbytes)
+    else:
+        run()
+
+
 def zero_page(device):
     key = (device.type, device.index)
     zp = _zero_pages.get(key)
@@ -187,7 +200,6 @@ def conv_gemm(x, wgt, nout, *, x1=None, n=None, h=None, w=None, kh=1, stride=1, 
     xattn = (k [images * keys_pad, heads * 64], vt [heads * 64, images * keys_pad], nk, keys_pad, queries_per_image, scale) with `ln`: the query
     projection of a cross-attention whose attention runs in the GEMM's epilogue (fmx.h xa_*): `out` receives the attention output, Q is never stored."""
     sfx, elem = _elem(x, x1, wgt, bias, rowvec, residual, gate)
-    fn_name = "fmx_gemm_conv" + sfx
     if out_dtype is None:
         out_dtype = elem
     if x.dim() == 2:
@@ -256,8 +268,7 @@ def conv_gemm(x, wgt, nout, *, x1=None, n=None, h=None, w=None, kh=1, stride=1, 
         got = C.c_int32(0)
 
         def launch():
-            _lib.check(_lib.lib().fmx_gemm_linear_rowstats_f16(C.byref(a), _p(row_stats.partial), cap, C.byref(got), stream_ptr()),
-                       "fmx_gemm_linear_rowstats_f16")
+            _call("fmx_gemm_linear_rowstats_f16", C.byref(a), _p(row_stats.partial), cap, C.byref(got))
             row_stats.parts = got.value
     elif stats and _FUSED_STATS:
         hw = oh * ow
@@ -268,19 +279,14 @@ def conv_gemm(x, wgt, nout, *, x1=None, n=None, h=None, w=None, kh=1, stride=1, 
         st = GnStats(partial, 0)
 
         def launch():
-            _lib.check(getattr(_lib.lib(), "fmx_gemm_conv_stats" + sfx)(C.byref(a), _p(partial), cap, fb, C.byref(nch), stream_ptr()),
-                       "fmx_gemm_conv_stats" + sfx)
+            _call("fmx_gemm_conv_stats" + sfx, C.byref(a), _p(partial), cap, fb, C.byref(nch))
             st.nchunks = nch.value
     else:
         def launch():
-            _lib.check(getattr(_lib.lib(), fn_name)(C.byref(a), stream_ptr()), fn_name)
-    if _profiler is not None:
-        flops = 2.0 * m * nout * kh * kh * (c0 + c1)
-        _profiler.launch("gemm_conv", flops, launch,
-                         tag=f"M={m} N={nout} K={kh * kh * (c0 + c1)} kh={kh} s={stride}{' up' if up else ''}{' geglu' if act == ACT_GEGLU else ''}"
-                             f"{' +gnstats' if st is not None else ''}{' +xattn' if xattn is not None else ''}")
-    else:
-        launch()
+            _call("fmx_gemm_conv" + sfx, C.byref(a))
+    _timed("gemm_conv", 2.0 * m * nout * kh * kh * (c0 + c1), launch,
+           tag=f"M={m} N={nout} K={kh * kh * (c0 + c1)} kh={kh} s={stride}{' up' if up else ''}{' geglu' if act == ACT_GEGLU else ''}"
+               f"{' +gnstats' if st is not None else ''}{' +xattn' if xattn is not None else ''}")
     _dbg(f"conv_gemm M={m} N={nout} K={kh * kh * (c0 + c1)} stats={st is not None and st.nchunks}", out=out,
          partial=None if st is None else st.partial.reshape(-1)[:n_ * st.nchunks * ncols * 2])
     return (out, st) if stats else out
@@ -303,8 +309,7 @@ def ln_rowstats_finalize(rs, c, eps):
     operand of the operand-swapped LayerNorm-folded GEMM (conv_gemm(ln_swapped=...))."""
     m = rs.partial.shape[0]
     ab = empty((m, 2), torch.float32, rs.partial.device)
-    _lib.check(_lib.lib().fmx_layernorm_rowstats_finalize(_p(rs.partial), rs.parts, m, c, float(eps), _p(ab), stream_ptr()),
-               "fmx_layernorm_rowstats_finalize")
+    _call("fmx_layernorm_rowstats_finalize", _p(rs.partial), rs.parts, m, c, float(eps), _p(ab))
     return ab
 
 
@@ -316,8 +321,7 @@ def geglu_interleave(w, b):
     inner = w.shape[0] // 2
     wo = torch.empty_like(w)
     bo = torch.empty_like(b) if b is not None else None
-    _lib.check(_lib.lib().fmx_geglu_interleave_rows(_p(w), _p(b), _p(wo), _p(bo), inner, w.shape[1], stream_ptr()),
-               "fmx_geglu_interleave_rows")
+    _call("fmx_geglu_interleave_rows", _p(w), _p(b), _p(wo), _p(bo), inner, w.shape[1])
     return wo, bo
 
 
@@ -334,7 +338,7 @@ def strided_copy4(src, dst, dims, src_strides, dst_strides):
     ss = (C.c_int64 * 4)(*[int(v) for v in src_strides])
     ds = (C.c_int64 * 4)(*[int(v) for v in dst_strides])
     dm = (C.c_int32 * 4)(*[int(v) for v in dims])
-    _lib.check(_lib.lib().fmx_strided_copy4(_p(src), _KINDS[src.dtype], ss, _p(dst), _KINDS[dst.dtype], ds, dm, stream_ptr()), "fmx_strided_copy4")
+    _call("fmx_strided_copy4", _p(src), _KINDS[src.dtype], ss, _p(dst), _KINDS[dst.dtype], ds, dm)
     return dst
 
 
@@ -345,7 +349,6 @@ def attention(q, k, vt, *, batch, heads, nq, nk, nk_pad, dpad, scale, q_bs, q_rs
     the images of O (default nq * out.stride(0): images back to back).
     mask: optional fp16 additive mask, element (b, h, i, j) at mask_strides = (batch, head, query) element strides, rows of nk_pad keys."""
     sfx, elem = _elem(q, k, vt, out)
-    fn_name = "fmx_attention" + sfx
     if out is None:
         out = empty((batch * nq, heads * dpad), elem, q.device)
     a = AttnArgs()
@@ -359,18 +362,12 @@ def attention(q, k, vt, *, batch, heads, nq, nk, nk_pad, dpad, scale, q_bs, q_rs
     a.causal = 1 if causal else 0
     a.mask = _p(mask)
     a.mask_bs, a.mask_hs, a.mask_qs = (int(v) for v in mask_strides)
-    if _profiler is not None:
-        d_true = int(round(float(scale) ** -2))
-        flops = 4.0 * batch * heads * nq * nk * d_true
-        # one key tile or two (the 77-token text context): no loop over keys, the launch is one read of Q + one write of O -> its own
-        # family with an HBM roofline (bench.py)
-        short = nk <= 128
-        _profiler.launch("attention_short_keys" if short else "attention", flops,
-                         lambda: _lib.check(getattr(_lib.lib(), fn_name)(C.byref(a), stream_ptr()), fn_name),
-                         tag=f"B={batch} H={heads} Nq={nq} Nk={nk} d={dpad}",
-                         nbytes=2.0 * batch * heads * dpad * (2 * nq + 2 * nk) if short else 0.0)
-        return out
-    _lib.check(getattr(_lib.lib(), fn_name)(C.byref(a), stream_ptr()), fn_name)
+    d_true = int(round(float(scale) ** -2)) if scale else dpad   # the FLOP count only: a zero scale is a legal launch
+    # one key tile or two (the 77-token text context): no loop over keys, the launch is one read of Q + one write of O -> its own
+    # family with an HBM roofline (bench.py)
+    short = nk <= 128
+    _timed("attention_short_keys" if short else "attention", 4.0 * batch * heads * nq * nk * d_true, lambda: _call("fmx_attention" + sfx, C.byref(a)),
+           tag=f"B={batch} H={heads} Nq={nq} Nk={nk} d={dpad}", nbytes=2.0 * batch * heads * dpad * (2 * nq + 2 * nk) if short else 0.0)
     return out
 
 
@@ -379,20 +376,16 @@ def attention_single_head512(q, k, vt, out, *, batch, nq, nk, nk_pad, q_bs, q_rs
     sfx, _ = _elem(q, k, vt, out)
 
     def launch():
-        _lib.check(getattr(_lib.lib(), "fmx_attention_single_head512" + sfx)(_p(q), q_bs, q_rs, _p(k), k_bs, k_rs, _p(vt), vt_bs, vt_ds, _p(out),
-                                                                             nq * out.stride(0), out.stride(0), batch, nq, nk, nk_pad, float(scale),
-                                                                             stream_ptr()), "fmx_attention_single_head512" + sfx)
-    if _profiler is not None:
-        _profiler.launch("attention", 4.0 * batch * nq * nk * 512, launch, tag=f"B={batch} H=1 Nq={nq} Nk={nk} d=512")
-    else:
-        launch()
+        _call("fmx_attention_single_head512" + sfx, _p(q), q_bs, q_rs, _p(k), k_bs, k_rs, _p(vt), vt_bs, vt_ds, _p(out), nq * out.stride(0), out.stride(0),
+              batch, nq, nk, nk_pad, float(scale))
+    _timed("attention", 4.0 * batch * nq * nk * 512, launch, tag=f"B={batch} H=1 Nq={nq} Nk={nk} d=512")
     _dbg(f"attention512 B={batch} N={nq}", out=out)
     return out
 
 
 def softmax_rows_(x):
     sfx, _ = _elem(x)
-    _lib.check(getattr(_lib.lib(), "fmx_softmax_rows" + sfx)(_p(x), x.shape[0], x.shape[1], x.stride(0), stream_ptr()), "fmx_softmax_rows" + sfx)
+    _call("fmx_softmax_rows" + sfx, _p(x), x.shape[0], x.shape[1], x.stride(0))
     return x
 
 
@@ -464,7 +457,7 @@ def groupnorm_stats(x):
     hw = x.numel() // (n * c)
     nch = _gn_chunks(n, hw)
     partial = empty((n, nch, c, 2), torch.float32, x.device)
-    _lib.check(getattr(_lib.lib(), "fmx_groupnorm_stats" + sfx)(_p(x), c, x.stride(-2), n, hw, _p(partial), nch, stream_ptr()), "fmx_groupnorm_stats" + sfx)
+    _call("fmx_groupnorm_stats" + sfx, _p(x), c, x.stride(-2), n, hw, _p(partial), nch)
     return GnStats(partial, nch)
 
 
@@ -489,16 +482,11 @@ def groupnorm(x, gamma, beta, eps, *, x1=None, silu=False, groups=32, out=None, 
         s0 = stats if stats is not None else groupnorm_stats(x)
         s1 = (stats1 if stats1 is not None else groupnorm_stats(x1)) if x1 is not None else None
         ss = empty((n, c0 + c1, 2), torch.float32, x.device)
-        _lib.check(getattr(_lib.lib(), "fmx_groupnorm_apply" + sfx)(_p(x), _p(x1), c0, c1, x.stride(-2), x1.stride(-2) if x1 is not None else 0, n, hw,
-                                                                    _p(s0.partial), s0.nchunks, _p(s1.partial) if s1 is not None else None,
-                                                                    s1.nchunks if s1 is not None else 0, groups, float(eps), _p(gamma), _p(beta),
-                                                                    1 if silu else 0, _p(ss), _p(out), stream_ptr()), "fmx_groupnorm_apply" + sfx)
-    if _profiler is not None:
-        have = (stats is not None) + (x1 is not None and stats1 is not None)
-        _profiler.launch("groupnorm", 0.0, run, tag=f"N={n} HW={hw} C={c0}+{c1} stats_from_producer={have}/{1 + (x1 is not None)}",
-                         nbytes=2.0 * 2 * n * hw * (c0 + c1))
-    else:
-        run()
+        _call("fmx_groupnorm_apply" + sfx, _p(x), _p(x1), c0, c1, x.stride(-2), x1.stride(-2) if x1 is not None else 0, n, hw, _p(s0.partial), s0.nchunks,
+              _p(s1.partial) if s1 is not None else None, s1.nchunks if s1 is not None else 0, groups, float(eps), _p(gamma), _p(beta), 1 if silu else 0,
+              _p(ss), _p(out))
+    have = (stats is not None) + (x1 is not None and stats1 is not None)
+    _timed("groupnorm", 0.0, run, tag=f"N={n} HW={hw} C={c0}+{c1} stats_from_producer={have}/{1 + (x1 is not None)}", nbytes=2.0 * 2 * n * hw * (c0 + c1))
     _dbg(f"groupnorm N={n} HW={hw} C={c0}+{c1} stats={'producer' if stats is not None else 'own'}/{'producer' if stats1 is not None else 'own'}", out=out)
     return out
 
@@ -509,7 +497,7 @@ def layernorm(x, gamma, beta, eps=1e-5, out=None):
     rows = x.numel() // c
     if out is None:
         out = empty(x.shape, torch.float16, x.device)
-    _lib.check(_lib.lib().fmx_layernorm_f16(_p(x), _p(gamma), _p(beta), _p(out), rows, c, float(eps), stream_ptr()), "fmx_layernorm_f16")
+    _call("fmx_layernorm_f16", _p(x), _p(gamma), _p(beta), _p(out), rows, c, float(eps))
     return out
 
 
@@ -520,7 +508,7 @@ def rmsnorm(x, weight, eps=1e-6, out=None):
     rows = x.numel() // c
     if out is None:
         out = empty(x.shape, elem, x.device)
-    _lib.check(getattr(_lib.lib(), "fmx_rmsnorm" + sfx)(_p(x), _p(weight), _p(out), rows, c, float(eps), stream_ptr()), "fmx_rmsnorm" + sfx)
+    _call("fmx_rmsnorm" + sfx, _p(x), _p(weight), _p(out), rows, c, float(eps))
     return out
 
 
@@ -530,8 +518,7 @@ def layernorm_padded(x, gamma, beta, out, rows_per_image, eps=1e-5):
     c = x.shape[-1]
     rows = x.numel() // c
     assert out.is_contiguous() and out.shape[-1] == c and out.shape[0] * rows_per_image == rows and out.shape[1] >= rows_per_image
-    _lib.check(_lib.lib().fmx_layernorm_padded_f16(_p(x), _p(gamma), _p(beta), _p(out), rows, c, float(eps), rows_per_image, out.shape[1],
-                                                   stream_ptr()), "fmx_layernorm_padded_f16")
+    _call("fmx_layernorm_padded_f16", _p(x), _p(gamma), _p(beta), _p(out), rows, c, float(eps), rows_per_image, out.shape[1])
     return out
 
 
@@ -543,8 +530,7 @@ def layernorm_mod(x, scale, shift, rows_per_batch, eps=1e-6, out=None):
     assert scale.stride(0) == shift.stride(0) and scale.stride(-1) == 1 and shift.stride(-1) == 1
     if out is None:
         out = empty(x.shape, elem, x.device)
-    _lib.check(getattr(_lib.lib(), "fmx_layernorm_mod" + sfx)(_p(x), _p(scale), _p(shift), scale.stride(0), rows_per_batch, _p(out), rows, c,
-                                                              float(eps), stream_ptr()), "fmx_layernorm_mod" + sfx)
+    _call("fmx_layernorm_mod" + sfx, _p(x), _p(scale), _p(shift), scale.stride(0), rows_per_batch, _p(out), rows, c, float(eps))
     return out
 
 
@@ -552,17 +538,15 @@ def flux_qk_norm_rope(qkv, q_scale, k_scale, pe, q_out, k_out, vt_out, *, batch,
     """qkv: [batch*tokens, >= 3*heads*head_dim] (row stride = qkv.stride(0)); pe: fp32 [L_total, head_dim/2, 2] (cos, sin)."""
     sfx, _ = _elem(qkv, q_scale, k_scale, q_out, k_out, vt_out)
     assert pe.dtype == torch.float32 and pe.is_contiguous()
-    _lib.check(getattr(_lib.lib(), "fmx_flux_qk_norm_rope" + sfx)(_p(qkv), qkv.stride(0), _p(q_scale), _p(k_scale), _p(pe), _p(q_out), _p(k_out),
-                                                                  _p(vt_out), batch, tokens, heads, head_dim, row_off, l_pad, float(eps),
-                                                                  stream_ptr()), "fmx_flux_qk_norm_rope" + sfx)
+    _call("fmx_flux_qk_norm_rope" + sfx, _p(qkv), qkv.stride(0), _p(q_scale), _p(k_scale), _p(pe), _p(q_out), _p(k_out), _p(vt_out), batch, tokens, heads,
+          head_dim, row_off, l_pad, float(eps))
 
 
 def timestep_embedding(t, dim, max_period=10000.0, out=None, dtype=torch.float16):
     b = t.shape[0]
     if out is None:
         out = empty((b, dim), dtype, t.device)
-    name = "fmx_timestep_embedding_bf16" if out.dtype == torch.bfloat16 else "fmx_timestep_embedding"
-    _lib.check(getattr(_lib.lib(), name)(_p(t), _p(out), b, dim, float(max_period), stream_ptr()), name)
+    _call("fmx_timestep_embedding_bf16" if out.dtype == torch.bfloat16 else "fmx_timestep_embedding", _p(t), _p(out), b, dim, float(max_period))
     return out
 
 
@@ -570,7 +554,7 @@ def silu(x, out=None):
     sfx, elem = _elem(x, out)
     if out is None:
         out = empty(x.shape, elem, x.device)
-    _lib.check(getattr(_lib.lib(), "fmx_silu" + sfx)(_p(x), _p(out), x.numel(), stream_ptr()), "fmx_silu" + sfx)
+    _call("fmx_silu" + sfx, _p(x), _p(out), x.numel())
     return out
 
 
@@ -586,17 +570,16 @@ def add_control_(h, ctrl, alpha=1.0):
     nhwc = ctrl.permute(0, 2, 3, 1)
     aligned = h.data_ptr() % 16 == 0 and nhwc.data_ptr() % 16 == 0
     if ctrl.device == h.device and nhwc.is_contiguous() and aligned and ctrl.dtype in (torch.float16, torch.float32) and not (c == 1 or hh * ww == 1):
-        _lib.check(_lib.lib().fmx_add_scaled_f16(_p(h), _p(nhwc), 1 if ctrl.dtype == torch.float32 else 0, float(alpha), h.numel(), stream_ptr()),
-                   "fmx_add_scaled_f16")
+        _call("fmx_add_scaled_f16", _p(h), _p(nhwc), 1 if ctrl.dtype == torch.float32 else 0, float(alpha), h.numel())
         return h
     if alpha != 1.0:
         ctrl = ctrl * alpha
     ctrl = ctrl.to(device=h.device, dtype=torch.float32).contiguous()
-    _lib.check(_lib.lib().fmx_add_control_nchw(_p(h), _p(ctrl), b, c, hh * ww, stream_ptr()), "fmx_add_control_nchw")
+    _call("fmx_add_control_nchw", _p(h), _p(ctrl), b, c, hh * ww)
     return h
 
 
-FREEU_CHUNK_PIXELS = 256      # FMX_FREEU_CHUNK_PIXELS of include/fmx.h
+FREEU_CHUNK_PIXELS = _lib.CONSTANTS["FMX_FREEU_CHUNK_PIXELS"]
 _freeu_trig = {}
 
 
@@ -613,7 +596,6 @@ def freeu_trig_table(hh, ww, device):
     key = (hh, ww, device.type, device.index)
     t = _freeu_trig.get(key)
     if t is None:
-        import math
         tr = [2.0 * math.pi * r / hh for r in range(hh)]
         tc = [2.0 * math.pi * c / ww for c in range(ww)]
         host = torch.tensor([math.cos(a) for a in tr] + [math.sin(a) for a in tr] + [math.cos(a) for a in tc] + [math.sin(a) for a in tc],
@@ -638,15 +620,12 @@ def freeu(h, skip, b, s):
     ws = empty((ws_floats,), torch.float32, h.device)
     clear_stats(h)
     clear_stats(skip)
-    L = _lib.lib()
-    _lib.check(L.fmx_freeu_reduce_f16(_p(h), c_h, _p(skip), c_s, n, hh, ww, _p(trig), nchunks, _p(ws), ws_floats, stream_ptr()), "fmx_freeu_reduce_f16")
-    _lib.check(L.fmx_freeu_apply_f16(_p(h), c_h, _p(skip), c_s, n, hh, ww, _p(trig), nchunks, _p(ws), ws_floats, float(b), float(s), stream_ptr()),
-               "fmx_freeu_apply_f16")
+    _call("fmx_freeu_reduce_f16", _p(h), c_h, _p(skip), c_s, n, hh, ww, _p(trig), nchunks, _p(ws), ws_floats)
+    _call("fmx_freeu_apply_f16", _p(h), c_h, _p(skip), c_s, n, hh, ww, _p(trig), nchunks, _p(ws), ws_floats, float(b), float(s))
     return h, skip
 
 
-DYNTHRESH_SEPARATE, DYNTHRESH_ZERO, DYNTHRESH_STD = 1, 2, 4   # FMX_DYNTHRESH_* of include/fmx.h
-DYNTHRESH_CHUNK = 2048
+DYNTHRESH_SEPARATE, DYNTHRESH_ZERO, DYNTHRESH_STD, DYNTHRESH_CHUNK = (_lib.CONSTANTS["FMX_DYNTHRESH_" + _n] for _n in ("SEPARATE", "ZERO", "STD", "CHUNK"))
 
 
 def _check_f32_rows(what, *ts):
@@ -665,8 +644,7 @@ def row_abs_quantile(x, center, q, rows_per_group=1):
     if rows_per_group <= 0 or rows % rows_per_group:
         raise ValueError(f"row_abs_quantile: {rows} rows are not whole groups of {rows_per_group}")
     out = torch.empty(rows // rows_per_group, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().fmx_row_abs_quantile_f32(_p(x), _p(center), rows, n, rows_per_group, float(q), _p(out), stream_ptr()),
-               "fmx_row_abs_quantile_f32")
+    _call("fmx_row_abs_quantile_f32", _p(x), _p(center), rows, n, rows_per_group, float(q), _p(out))
     return out
 
 
@@ -689,8 +667,7 @@ def dynthresh(cond, uncond, mimic, cfg, percentile, separate, startpoint, variab
             raise ValueError("dynthresh: out must have the inputs' shape")
     flags = (DYNTHRESH_SEPARATE if separate else 0) | (DYNTHRESH_ZERO if startpoint == "ZERO" else 0) | (DYNTHRESH_STD if variability == "STD" else 0)
     ws = torch.empty(b * c * (-(-hw // DYNTHRESH_CHUNK)) * 2 + b * c * 4, dtype=torch.float32, device=cond.device)   # FMX_DYNTHRESH_WORKSPACE_FLOATS
-    _lib.check(_lib.lib().fmx_dynthresh_f32(_p(cond), _p(uncond), b, c, hw, float(mimic), float(cfg), float(percentile), flags, float(phi), _p(ws),
-                                            _p(out), stream_ptr()), "fmx_dynthresh_f32")
+    _call("fmx_dynthresh_f32", _p(cond), _p(uncond), b, c, hw, float(mimic), float(cfg), float(percentile), flags, float(phi), _p(ws), _p(out))
     return out
 
 
@@ -701,14 +678,14 @@ def avgpool2x2(x):
     """fp16 NHWC [N, H, W, C] -> [N, H/2, W/2, C]"""
     n, h, w, c = x.shape
     out = empty((n, h // 2, w // 2, c), torch.float16, x.device)
-    _lib.check(_lib.lib().fmx_avgpool2x2_nhwc_f16(_p(x), _p(out), n, h, w, c, stream_ptr()), "fmx_avgpool2x2_nhwc_f16")
+    _call("fmx_avgpool2x2_nhwc_f16", _p(x), _p(out), n, h, w, c)
     return out
 
 
 def act(x, kind, out=None):
     if out is None:
         out = empty(x.shape, torch.float16, x.device)
-    _lib.check(_lib.lib().fmx_act_f16(_p(x), _p(out), x.numel(), int(kind), stream_ptr()), "fmx_act_f16")
+    _call("fmx_act_f16", _p(x), _p(out), x.numel(), int(kind))
     return out
 
 
@@ -718,14 +695,14 @@ def embed_tokens(ids, tok_emb, pos_emb, out=None):
     c = tok_emb.shape[1]
     if out is None:
         out = empty((b * t, c), torch.float16, ids.device)
-    _lib.check(_lib.lib().fmx_embed_tokens(_p(ids), _p(tok_emb), _p(pos_emb), _p(out), b, t, c, tok_emb.shape[0], stream_ptr()), "fmx_embed_tokens")
+    _call("fmx_embed_tokens", _p(ids), _p(tok_emb), _p(pos_emb), _p(out), b, t, c, tok_emb.shape[0])
     return out
 
 
 def cast_f16(x, out=None):
     if out is None:
         out = empty(x.shape, torch.float16, x.device)
-    _lib.check(_lib.lib().fmx_cast_f32_to_f16(_p(x), _p(out), x.numel(), stream_ptr()), "fmx_cast_f32_to_f16")
+    _call("fmx_cast_f32_to_f16", _p(x), _p(out), x.numel())
     return out
 
 
@@ -746,7 +723,7 @@ def gguf_dequant(raw, qtype, shape, dtype=torch.bfloat16, out=None):
         raise ValueError("gguf_dequant: %d bytes do not hold %s %s weights" % (raw.numel(), shape, GGML_TYPES[qtype][0]))
     if out is None:
         out = empty(shape, dtype, raw.device)
-    _lib.check(getattr(_lib.lib(), "fmx_gguf_dequant" + sfx)(int(qtype), _p(raw), _p(out), n, stream_ptr()), "fmx_gguf_dequant" + sfx)
+    _call("fmx_gguf_dequant" + sfx, int(qtype), _p(raw), _p(out), n)
     return out
 
 
@@ -788,7 +765,7 @@ def fp8_expand(raw, kind, shape, dtype=torch.bfloat16, out=None):
     if raw.numel() != n:
         raise ValueError("fp8_expand: %d bytes do not hold %s float8 weights" % (raw.numel(), shape))
     out = _expanded_out("fp8_expand", out, shape, n, dtype, raw.device)
-    _lib.check(getattr(_lib.lib(), "fmx_fp8_expand" + sfx)(int(FP8_KINDS.get(kind, kind)), _p(raw), _p(out), n, stream_ptr()), "fmx_fp8_expand" + sfx)
+    _call("fmx_fp8_expand" + sfx, int(FP8_KINDS.get(kind, kind)), _p(raw), _p(out), n)
     return out
 
 
@@ -823,7 +800,7 @@ def bnb4_dequant(packed, quant_state, dtype=torch.bfloat16, out=None):
     else:
         args = (_p(side(qs.absmax, "absmax", torch.float32, nblocks)), None, None, None, 0.0, 0)
     out = _expanded_out("bnb4_dequant", out, shape, n, dtype, packed.device)
-    _lib.check(getattr(_lib.lib(), "fmx_bnb4_dequant" + sfx)(_p(packed), _p(code), *args, bs, _p(out), n, stream_ptr()), "fmx_bnb4_dequant" + sfx)
+    _call("fmx_bnb4_dequant" + sfx, _p(packed), _p(code), *args, bs, _p(out), n)
     return out
 
 
@@ -831,8 +808,7 @@ def unet_pack_input(x, sigma, reps, sigma_data=1.0, out=None):
     b, c, h, w = x.shape
     if out is None:
         out = empty((reps * b * h * w, 64), torch.float16, x.device)
-    _lib.check(_lib.lib().fmx_unet_pack_input(_p(x), _p(sigma), float(sigma_data), b, c, h, w, reps, _p(out), stream_ptr()),
-               "fmx_unet_pack_input")
+    _call("fmx_unet_pack_input", _p(x), _p(sigma), float(sigma_data), b, c, h, w, reps, _p(out))
     return out
 
 
@@ -840,7 +816,7 @@ def im2col3x3_smallc(x, c, out=None):
     n, h, w, ld = x.shape
     if out is None:
         out = empty((n * h * w, 64), x.dtype, x.device)    # a 16-bit word shuffle: fp16 and bf16 alike
-    _lib.check(_lib.lib().fmx_im2col3x3_smallc(_p(x), ld, n, c, h, w, _p(out), stream_ptr()), "fmx_im2col3x3_smallc")
+    _call("fmx_im2col3x3_smallc", _p(x), ld, n, c, h, w, _p(out))
     return out
 
 
@@ -852,9 +828,8 @@ def cfg_combine(eps, ld_eps, x, sigma, reps, cond_scale, denoised=None, cond_pre
     b, c, h, w = x.shape
     if denoised is None:
         denoised = torch.empty_like(x)
-    _lib.check(_lib.lib().fmx_cfg_combine(_p(eps), ld_eps, _p(x), _p(sigma), b, c, h, w, reps, float(cond_scale), _p(denoised),
-                                          _p(cond_pred), _p(uncond_pred), PREDICTION_TYPES[prediction_type], float(sigma_data), stream_ptr()),
-               "fmx_cfg_combine")
+    _call("fmx_cfg_combine", _p(eps), ld_eps, _p(x), _p(sigma), b, c, h, w, reps, float(cond_scale), _p(denoised), _p(cond_pred), _p(uncond_pred),
+          PREDICTION_TYPES[prediction_type], float(sigma_data))
     return denoised
 
 
@@ -866,9 +841,8 @@ def cfg_pag_combine(eps, ld_eps, x, sigma, has_uncond, cond_scale, pag_scale, de
     b, c, h, w = x.shape
     if denoised is None:
         denoised = torch.empty_like(x)
-    _lib.check(_lib.lib().fmx_cfg_pag_combine(_p(eps), ld_eps, _p(x), _p(sigma), b, c, h, w, 1 if has_uncond else 0, float(cond_scale),
-                                              float(pag_scale), _p(denoised), _p(cond_pred), _p(uncond_pred), _p(degraded_pred),
-                                              PREDICTION_TYPES[prediction_type], float(sigma_data), stream_ptr()), "fmx_cfg_pag_combine")
+    _call("fmx_cfg_pag_combine", _p(eps), ld_eps, _p(x), _p(sigma), b, c, h, w, 1 if has_uncond else 0, float(cond_scale), float(pag_scale), _p(denoised),
+          _p(cond_pred), _p(uncond_pred), _p(degraded_pred), PREDICTION_TYPES[prediction_type], float(sigma_data))
     return denoised
 
 
@@ -877,31 +851,27 @@ def attn_value_rows(vt, out, *, first, count, n, hd, vt_bs, vt_ds, o_bs=None):
     images.  vt / out / the strides are ops.attention's V^T operand and O (out: [rows, >= hd] view, stride(0) the row stride; o_bs defaults to
     n * out.stride(0))."""
     _check_f16(vt, out)
-    _lib.check(_lib.lib().fmx_attn_value_rows_f16(_p(vt), int(vt_bs), int(vt_ds), _p(out), out.stride(0),
-                                                  n * out.stride(0) if o_bs is None else int(o_bs), hd, n, first, count, stream_ptr()),
-               "fmx_attn_value_rows_f16")
+    _call("fmx_attn_value_rows_f16", _p(vt), int(vt_bs), int(vt_ds), _p(out), out.stride(0), n * out.stride(0) if o_bs is None else int(o_bs), hd, n,
+          first, count)
     return out
 
 
 def euler_step(x, denoised, sigma, sigma_next, noise=None, noise_scale=0.0, out=None):
     if out is None:
         out = torch.empty_like(x)
-    _lib.check(_lib.lib().fmx_sampler_euler_step(_p(x), _p(denoised), float(sigma), float(sigma_next), _p(noise), float(noise_scale),
-                                                 _p(out), x.numel(), stream_ptr()), "fmx_sampler_euler_step")
+    _call("fmx_sampler_euler_step", _p(x), _p(denoised), float(sigma), float(sigma_next), _p(noise), float(noise_scale), _p(out), x.numel())
     return out
 
 
 def lincomb3(x, d0, d1, a, b, c, out=None):
     if out is None:
         out = torch.empty_like(x)
-    _lib.check(_lib.lib().fmx_sampler_lincomb3(_p(x), _p(d0), _p(d1), float(a), float(b), float(c), _p(out), x.numel(), stream_ptr()),
-               "fmx_sampler_lincomb3")
+    _call("fmx_sampler_lincomb3", _p(x), _p(d0), _p(d1), float(a), float(b), float(c), _p(out), x.numel())
     return out
 
 
 def lincomb(srcs, coefs, out=None):
     """out = sum_k coefs[k] * srcs[k] over fp32 tensors of one shape; one fused pass per 8 terms."""
-    import ctypes
     n = len(srcs)
     assert n >= 1 and n == len(coefs)
     if n > 8:  # more terms than one launch takes (UniPC at order > 5): accumulate in groups, the partial sum riding along as term 0
@@ -914,10 +884,9 @@ def lincomb(srcs, coefs, out=None):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == x.shape and t.device == x.device
     if out is None:
         out = torch.empty_like(x)
-    ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in srcs])
-    cf = (ctypes.c_float * n)(*[float(c) for c in coefs])
-    _lib.check(_lib.lib().fmx_sampler_lincomb(ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(cf, ctypes.c_void_p), n, _p(out), x.numel(),
-                                              stream_ptr()), "fmx_sampler_lincomb")
+    ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in srcs])
+    cf = (C.c_float * n)(*[float(c) for c in coefs])
+    _call("fmx_sampler_lincomb", C.cast(ptrs, C.c_void_p), C.cast(cf, C.c_void_p), n, _p(out), x.numel())
     return out
 
 
@@ -925,8 +894,7 @@ def error_norm(x_low, x_high, x_prev, atol, rtol):
     """-> python float: ||(x_low - x_high) / max(atol, rtol * max(|x_low|, |x_prev|))|| / sqrt(numel) (one device sync: the adaptive
     step-size controller needs the value on the host to accept / reject the step)."""
     ws = torch.empty(257, dtype=torch.float32, device=x_low.device)
-    _lib.check(_lib.lib().fmx_sampler_error_norm(_p(x_low), _p(x_high), _p(x_prev), float(atol), float(rtol), _p(ws), ws[256:].data_ptr(),
-                                                 x_low.numel(), stream_ptr()), "fmx_sampler_error_norm")
+    _call("fmx_sampler_error_norm", _p(x_low), _p(x_high), _p(x_prev), float(atol), float(rtol), _p(ws), ws[256:].data_ptr(), x_low.numel())
     return float(ws[256])
 
 
@@ -941,8 +909,7 @@ def resize_separable(x, ystart, yweights, xstart, xweights):
     xs, xw = xstart.to(device=dev, dtype=torch.int32).contiguous(), xweights.to(device=dev, dtype=torch.float32).contiguous()
     out = torch.empty(x.shape[:-2] + (oh, ow), dtype=torch.float32, device=dev)
     planes = x.numel() // (h * w)
-    _lib.check(_lib.lib().fmx_resize_separable_f32(_p(x), _p(out), _p(ys), _p(yw), _p(xs), _p(xw), planes, h, w, oh, ow, ky, kx, stream_ptr()),
-               "fmx_resize_separable_f32")
+    _call("fmx_resize_separable_f32", _p(x), _p(out), _p(ys), _p(yw), _p(xs), _p(xw), planes, h, w, oh, ow, ky, kx)
     return out
 
 
@@ -975,15 +942,14 @@ def resize_nhwc(x, size, mode="bicubic"):
     oh, ow = int(size[0]), int(size[1])
     ys, yw, xs, xw = resize_nhwc_tables(h, w, oh, ow, mode, x.device)
     out = empty((n, oh, ow, c), torch.float16, x.device)
-    _lib.check(_lib.lib().fmx_resize_nhwc_f16(_p(x), _p(out), _p(ys), _p(yw), _p(xs), _p(xw), n, h, w, c, oh, ow, yw.shape[1], xw.shape[1],
-                                              stream_ptr()), "fmx_resize_nhwc_f16")
+    _call("fmx_resize_nhwc_f16", _p(x), _p(out), _p(ys), _p(yw), _p(xs), _p(xw), n, h, w, c, oh, ow, yw.shape[1], xw.shape[1])
     return out
 
 
 def scale_f32(x, s, out=None):
     if out is None:
         out = torch.empty_like(x)
-    _lib.check(_lib.lib().fmx_scale_f32(_p(x), float(s), _p(out), x.numel(), stream_ptr()), "fmx_scale_f32")
+    _call("fmx_scale_f32", _p(x), float(s), _p(out), x.numel())
     return out
 
 
@@ -994,7 +960,7 @@ def blend_masked(a, a_mask, b, b_mask, out=None):
             raise TypeError("blend_masked expects contiguous fp32 device tensors of one shape")
     if out is None:
         out = torch.empty_like(a)
-    _lib.check(_lib.lib().fmx_blend_masked(_p(a), _p(a_mask), _p(b), _p(b_mask), _p(out), a.numel(), stream_ptr()), "fmx_blend_masked")
+    _call("fmx_blend_masked", _p(a), _p(a_mask), _p(b), _p(b_mask), _p(out), a.numel())
     return out
 
 
@@ -1006,8 +972,7 @@ def vae_pack_latent(z, scaling_factor, shift, ld=8, out=None, dtype=torch.float1
     b, c, h, w = z.shape
     if out is None:
         out = empty((b, h, w, ld), dtype, z.device)
-    name = "fmx_vae_pack_latent" + _vae_sfx(out.dtype)
-    _lib.check(getattr(_lib.lib(), name)(_p(z), float(scaling_factor), float(shift), b, c, h, w, _p(out), ld, stream_ptr()), name)
+    _call("fmx_vae_pack_latent" + _vae_sfx(out.dtype), _p(z), float(scaling_factor), float(shift), b, c, h, w, _p(out), ld)
     return out
 
 
@@ -1016,8 +981,7 @@ def vae_sample_posterior(moments, ld, noise, lc, scale=1.0, shift=0.0, out=None)
     b, _, hh, ww = noise.shape
     if out is None:
         out = torch.empty_like(noise)
-    name = "fmx_vae_sample_posterior" + _vae_sfx(moments.dtype)
-    _lib.check(getattr(_lib.lib(), name)(_p(moments), ld, _p(noise), b, lc, hh * ww, float(scale), float(shift), _p(out), stream_ptr()), name)
+    _call("fmx_vae_sample_posterior" + _vae_sfx(moments.dtype), _p(moments), ld, _p(noise), b, lc, hh * ww, float(scale), float(shift), _p(out))
     return out
 
 
@@ -1028,7 +992,7 @@ def count_nonfinite(x, cnt=None):
     assert x.is_contiguous()
     if cnt is None:
         cnt = torch.empty(1, dtype=torch.int32, device=x.device)
-    _lib.check(_lib.lib().fmx_count_nonfinite_f16(_p(x), x.numel(), _p(cnt), stream_ptr()), "fmx_count_nonfinite_f16")
+    _call("fmx_count_nonfinite_f16", _p(x), x.numel(), _p(cnt))
     return int(cnt.item())
 
 
@@ -1039,14 +1003,11 @@ def conv3x3_narrow(x, wgt, bias, nout, out=None, ld_out=4):
     n, h, w, c = x.shape
     if out is None:
         out = empty((n * h * w, ld_out), elem, x.device)
-    name = "fmx_conv3x3_narrow" + sfx
 
     def run():
-        _lib.check(getattr(_lib.lib(), name)(_p(x), n, h, w, c, _p(wgt), _p(bias), nout, _p(out), ld_out, stream_ptr()), name)
-    if _profiler is not None:   # HBM-bound: one read of the input, one write of the [npix, ld_out] output
-        _profiler.launch("conv3x3_narrow", 2.0 * n * h * w * 9 * c * nout, run, tag=f"N={n} H={h} W={w} C={c} nout={nout}", nbytes=2.0 * n * h * w * (c + ld_out))
-    else:
-        run()
+        _call("fmx_conv3x3_narrow" + sfx, _p(x), n, h, w, c, _p(wgt), _p(bias), nout, _p(out), ld_out)
+    # HBM-bound: one read of the input, one write of the [npix, ld_out] output
+    _timed("conv3x3_narrow", 2.0 * n * h * w * 9 * c * nout, run, tag=f"N={n} H={h} W={w} C={c} nout={nout}", nbytes=2.0 * n * h * w * (c + ld_out))
     return out
 
 
@@ -1064,16 +1025,13 @@ def conv3x3_c64(x, wgt, bias=None, *, residual=None, relu=False, up2x=False, out
     for t in (out, residual):
         if t is not None and (t.dim() != 2 or t.shape[0] != m or t.shape[1] < 64 or t.stride(1) != 1):
             raise ValueError("conv3x3_c64: out / residual must be [n * oh * ow, >= 64] with unit column stride")
-    name = "fmx_conv3x3_c64" + sfx
 
     def run():
-        _lib.check(getattr(_lib.lib(), name)(_p(x), n, h, w, c, _p(wgt), _p(bias), wgt.shape[0], _p(residual), residual.stride(0) if residual is not None else 0,
-                                             int(bool(relu)), int(bool(up2x)), _p(out), out.stride(0), stream_ptr()), name)
-    if _profiler is not None:   # one read of the input (a quarter of it with up2x) and of the residual, one write of the output
-        _profiler.launch("conv3x3_c64", 2.0 * m * 9 * 64 * 64, run, tag=f"N={n} H={h} W={w} up2x={int(up2x)} relu={int(relu)} res={int(residual is not None)}",
-                         nbytes=2.0 * 64 * (n * h * w + m * (2 if residual is not None else 1)))
-    else:
-        run()
+        _call("fmx_conv3x3_c64" + sfx, _p(x), n, h, w, c, _p(wgt), _p(bias), wgt.shape[0], _p(residual), residual.stride(0) if residual is not None else 0,
+              int(bool(relu)), int(bool(up2x)), _p(out), out.stride(0))
+    # one read of the input (a quarter of it with up2x) and of the residual, one write of the output
+    _timed("conv3x3_c64", 2.0 * m * 9 * 64 * 64, run, tag=f"N={n} H={h} W={w} up2x={int(up2x)} relu={int(relu)} res={int(residual is not None)}",
+           nbytes=2.0 * 64 * (n * h * w + m * (2 if residual is not None else 1)))
     return out
 
 
@@ -1098,15 +1056,10 @@ def conv3x3_dense(x, cin, wgt, bias=None, *, slope=1.0, res1=None, alpha=1.0, re
             raise ValueError("conv3x3_dense: out / res1 / res2 must be [n * oh * ow, >= cout] with unit column stride")
 
     def run():
-        _lib.check(_lib.lib().fmx_conv3x3_dense_f16(_p(x), ld_x, n, h, w, cin, _p(wgt), _p(bias), cout, float(slope), _p(res1),
-                                                    res1.stride(0) if res1 is not None else 0, float(alpha), _p(res2), res2.stride(0) if res2 is not None else 0,
-                                                    float(beta), int(bool(up2x)), _p(out), out.stride(0), stream_ptr()), "fmx_conv3x3_dense_f16")
-    if _profiler is not None:
-        nres = (res1 is not None) + (res2 is not None)
-        _profiler.launch("conv3x3_dense", 2.0 * m * 9 * cin * cout, run, tag=f"cin={cin} cout={cout} up2x={int(up2x)}",
-                         nbytes=2.0 * (n * h * w * cin + m * cout * (1 + nres)))
-    else:
-        run()
+        _call("fmx_conv3x3_dense_f16", _p(x), ld_x, n, h, w, cin, _p(wgt), _p(bias), cout, float(slope), _p(res1), res1.stride(0) if res1 is not None else 0,
+              float(alpha), _p(res2), res2.stride(0) if res2 is not None else 0, float(beta), int(bool(up2x)), _p(out), out.stride(0))
+    nres = (res1 is not None) + (res2 is not None)
+    _timed("conv3x3_dense", 2.0 * m * 9 * cin * cout, run, tag=f"cin={cin} cout={cout} up2x={int(up2x)}", nbytes=2.0 * (n * h * w * cin + m * cout * (1 + nres)))
     return out
 
 
@@ -1134,7 +1087,7 @@ def esrgan_pack_image(img, out=None):
     _check_f16(out)
     if not out.is_contiguous() or out.numel() != n * h * w * 64:
         raise ValueError("esrgan_pack_image: out must be a contiguous [n, h, w, 64] tensor")
-    _lib.check(_lib.lib().fmx_esrgan_pack_image(_p(img), _p(esrgan_lut(img.device)), n * h * w, _p(out), stream_ptr()), "fmx_esrgan_pack_image")
+    _call("fmx_esrgan_pack_image", _p(img), _p(esrgan_lut(img.device)), n * h * w, _p(out))
     return out
 
 
@@ -1148,7 +1101,7 @@ def esrgan_unpack_image(y, out=None):
         out = empty((npix, 3), torch.uint8, y.device)
     if out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != npix * 3:
         raise ValueError("esrgan_unpack_image: out must be a contiguous uint8 [npix, 3] tensor")
-    _lib.check(_lib.lib().fmx_esrgan_unpack_image(_p(y), y.stride(0), npix, _p(out), stream_ptr()), "fmx_esrgan_unpack_image")
+    _call("fmx_esrgan_unpack_image", _p(y), y.stride(0), npix, _p(out))
     return out
 
 
@@ -1159,8 +1112,7 @@ def taesd_pack_latent(z, out=None, dtype=torch.float16):
     b, c, h, w = z.shape
     if out is None:
         out = empty((b, h, w, 64), dtype, z.device)
-    name = "fmx_taesd_pack_latent" + _vae_sfx(out.dtype)
-    _lib.check(getattr(_lib.lib(), name)(_p(z), b, c, h, w, _p(out), stream_ptr()), name)
+    _call("fmx_taesd_pack_latent" + _vae_sfx(out.dtype), _p(z), b, c, h, w, _p(out))
     return out
 
 
@@ -1174,7 +1126,7 @@ def latent_rgb(z, factors, out=None):
         raise ValueError(f"latent_rgb: the factor table must be [{l}][3], got {len(flat)} values")
     if out is None:
         out = torch.empty((b, 3, h, w), dtype=torch.float32, device=z.device)
-    _lib.check(_lib.lib().fmx_latent_rgb(_p(z), (C.c_float * len(flat))(*flat), b, l, h * w, _p(out), stream_ptr()), "fmx_latent_rgb")
+    _call("fmx_latent_rgb", _p(z), (C.c_float * len(flat))(*flat), b, l, h * w, _p(out))
     return out
 
 
@@ -1240,17 +1192,13 @@ def conv3x3_up2x(x, w4, bias, nout, *, stats=True, stats_partial=None):
         cap = partial.numel() // (n * nout * 2)
         st = GnStats(partial, 0)
     nch = C.c_int32(0)
-    name = "fmx_conv3x3_up2x" + sfx
 
     def run():
-        _lib.check(getattr(_lib.lib(), name)(_p(x), n, h, w, c, _p(w4), _p(bias), nout, _p(out), _p(partial), cap, C.byref(nch), _p(zero_page(x.device)),
-                                            stream_ptr()), name)
+        _call("fmx_conv3x3_up2x" + sfx, _p(x), n, h, w, c, _p(w4), _p(bias), nout, _p(out), _p(partial), cap, C.byref(nch), _p(zero_page(x.device)))
         if st is not None:
             st.nchunks = nch.value
-    if _profiler is not None:   # the multiply-adds EXECUTED: 4 taps per output pixel (the reference's form of the layer has 9)
-        _profiler.launch("gemm_conv", 2.0 * n * 4 * h * w * nout * 4 * c, run, tag=f"M={n * 4 * h * w} N={nout} K={4 * c} kh=2 s=1 up2x-phases{' +gnstats' if st is not None else ''}")
-    else:
-        run()
+    # the multiply-adds EXECUTED: 4 taps per output pixel (the reference's form of the layer has 9)
+    _timed("gemm_conv", 2.0 * n * 4 * h * w * nout * 4 * c, run, tag=f"M={n * 4 * h * w} N={nout} K={4 * c} kh=2 s=1 up2x-phases{' +gnstats' if st is not None else ''}")
     return (out, st) if stats else out
 
 
@@ -1297,17 +1245,22 @@ def conv3x3_gn_silu(x, gamma, beta, eps, wgt, bias, *, residual=None, out=None, 
         partial = stats_partial if stats_partial is not None else empty((n, cap, cout, 2), torch.float32, x.device)
         a.stats, a.stats_cap = _p(partial), partial.numel() // (n * cout * 2)
         st = GnStats(partial, 0)
-    name = "fmx_conv3x3_gn_silu" + sfx
 
     def run():
-        _lib.check(getattr(_lib.lib(), name)(C.byref(a), C.byref(nch), stream_ptr()), name)
+        _call("fmx_conv3x3_gn_silu" + sfx, C.byref(a), C.byref(nch))
         if st is not None:
             st.nchunks = nch.value
-    if _profiler is not None:
-        _profiler.launch("gemm_conv", 2.0 * n * h * w * cout * 9 * cin, run, tag=f"M={n * h * w} N={cout} K={9 * cin} kh=3 s=1 gn+silu fused{' +gnstats' if st is not None else ''}")
-    else:
-        run()
+    _timed("gemm_conv", 2.0 * n * h * w * cout * 9 * cin, run, tag=f"M={n * h * w} N={cout} K={9 * cin} kh=3 s=1 gn+silu fused{' +gnstats' if st is not None else ''}")
     return out, st
+
+
+def conv3x3_narrow_gn_silu_eligible(x, nout):
+    """where the executors put GroupNorm + SiLU into the narrow-output convolution's staging (conv3x3_narrow_gn_silu) instead of a groupnorm() launch in
+    front of conv3x3_narrow(): a contiguous NHWC tensor, channels in 32s, at most 4 output channels, statistics left on x by its producer, and at
+    least 2^16 pixels (the tails of the VAE decoder and of the UNet)"""
+    if not _CONV_GN_FUSE or x.dim() != 4 or nout > 4 or x.shape[-1] % 32 or not x.is_contiguous():
+        return False
+    return _attached_stats(x) is not None and x.shape[0] * x.shape[1] * x.shape[2] >= (1 << 16)
 
 
 def conv3x3_narrow_gn_silu(x, gamma, beta, eps, wgt, bias, nout, *, groups=32, out=None, ld_out=4, stats=None):
@@ -1320,27 +1273,22 @@ def conv3x3_narrow_gn_silu(x, gamma, beta, eps, wgt, bias, nout, *, groups=32, o
     if out is None:
         out = empty((n * h * w, ld_out), elem, x.device)
     ss = empty((n, c, 2), torch.float32, x.device)
-    name = "fmx_conv3x3_narrow_gn_silu" + sfx
 
     def run():
-        _lib.check(getattr(_lib.lib(), name)(_p(x), n, h, w, c, _p(s0.partial), s0.nchunks, groups, float(eps), _p(gamma), _p(beta), _p(ss), _p(wgt), _p(bias), nout,
-                                            _p(out), ld_out, stream_ptr()), name)
-    if _profiler is not None:   # HBM-bound: one read of the input, one write of the [npix, ld_out] output
-        _profiler.launch("conv3x3_narrow", 2.0 * n * h * w * 9 * c * nout, run, tag=f"N={n} H={h} W={w} C={c} nout={nout} gn+silu fused", nbytes=2.0 * n * h * w * (c + ld_out))
-    else:
-        run()
+        _call("fmx_conv3x3_narrow_gn_silu" + sfx, _p(x), n, h, w, c, _p(s0.partial), s0.nchunks, groups, float(eps), _p(gamma), _p(beta), _p(ss), _p(wgt), _p(bias),
+              nout, _p(out), ld_out)
+    # HBM-bound: one read of the input, one write of the [npix, ld_out] output
+    _timed("conv3x3_narrow", 2.0 * n * h * w * 9 * c * nout, run, tag=f"N={n} H={h} W={w} C={c} nout={nout} gn+silu fused", nbytes=2.0 * n * h * w * (c + ld_out))
     return out
 
 
 def vae_unpack_image(y, ld, npix, c, out):
-    name = "fmx_vae_unpack_image" + _vae_sfx(y.dtype)
-    _lib.check(getattr(_lib.lib(), name)(_p(y), ld, npix, c, _p(out), stream_ptr()), name)
+    _call("fmx_vae_unpack_image" + _vae_sfx(y.dtype), _p(y), ld, npix, c, _p(out))
     return out
 
 
 def philox_randn(seed, offset, n, device, want_raw=False):
     out = torch.empty(n, dtype=torch.float32, device=device)
     raw = torch.empty((n, 4), dtype=torch.int32, device=device) if want_raw else None
-    _lib.check(_lib.lib().fmx_philox_randn(C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint32(int(offset)), _p(out), _p(raw), n, stream_ptr()),
-               "fmx_philox_randn")
+    _call("fmx_philox_randn", C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint32(int(offset)), _p(out), _p(raw), n)
     return (out, raw) if want_raw else out
