@@ -1,4 +1,4 @@
-"""ctypes binding of libfmx_gfx950.so (C-ABI declared in include/fmx.h).
+"""ctypes binding of libfmx_gfx950.so (C-ABI declared in include/fmx.h; include/fmx_ext.h holds entry points not yet declared there).
 
 The library is built in-tree by `build()` (hipcc --offload-arch=gfx950) so that it travels with the
 repo snapshot.  There is deliberately NO fallback: if the shared object is missing or a symbol is
@@ -51,14 +51,15 @@ _STRUCT_NAMES = {"fmx_gemm_args": "GemmArgs", "fmx_attn_args": "AttnArgs", "fmx_
 _PARAM = re.compile(r"(?:const )?(\w+) ?((?:\* ?(?:const ?)?)*)(\w+)?")
 
 
-def parse_header(text):
-    """The text of include/fmx.h -> (signatures, accessors, structs, constants): {name: [ctypes of the parameters]} of every `int fmx_*(...);`
+def parse_header(text, prefix="fmx_", known_structs=None):
+    """The text of include/fmx.h (or, with prefix "fmxe_" and fmx.h's structs, of include/fmx_ext.h) -> (signatures, accessors, structs, constants):
+    {name: [ctypes of the parameters]} of every `int fmx_*(...);`
     prototype, the names of the `const char* fmx_*(void);` accessors, {C name: ctypes.Structure class} of every `typedef struct fmx_x {...} fmx_x;`
     and {name: int} of every `#define NAME <integer literal>`.  Scalars map through _SCALARS; a pointer to one of the structs is POINTER(struct),
     `char*` is c_char_p, every other pointer -- and every pointer field of a struct -- c_void_p.  Whatever is left between the declarations and
     does not parse as one of these forms raises FmxError naming the text: nothing is skipped."""
     def bad(what):
-        return FmxError(f"include/fmx.h: cannot bind {' '.join(what.split())!r}")
+        return FmxError(f"include/{'fmx.h' if prefix == 'fmx_' else 'fmx_ext.h'}: cannot bind {' '.join(what.split())!r}")
 
     def scalar(ctype, where):
         if ctype not in _SCALARS:
@@ -76,7 +77,7 @@ def parse_header(text):
             code.append(line)
     text = re.sub(r'extern\s+"C"\s*\{(.*)\}', r"\1", " ".join(code), flags=re.S)
 
-    structs = {}
+    structs = dict(known_structs or {})
 
     def struct(m):
         if m.group(1) != m.group(3):
@@ -97,7 +98,7 @@ def parse_header(text):
 
     signatures, accessors = {}, []
     for stmt in filter(None, (" ".join(s.split()) for s in text.split(";"))):
-        m = re.fullmatch(r"(int|const char ?\*) ?(fmx_\w+) ?\((.*)\)", stmt)
+        m = re.fullmatch(r"(int|const char ?\*) ?(" + re.escape(prefix) + r"\w+) ?\((.*)\)", stmt)
         if not m or m.group(2) in signatures or m.group(2) in accessors:
             raise bad(stmt)
         params = [] if m.group(3).strip() == "void" else [p.strip() for p in m.group(3).split(",")]
@@ -122,17 +123,21 @@ def parse_header(text):
     return signatures, accessors, structs, constants
 
 
-def _read_header():
+def _read_header(path=None):
+    path = path or HEADER
     try:
-        with open(HEADER) as f:
+        with open(path) as f:
             return f.read()
     except OSError as e:
-        raise FmxError(f"{HEADER} not found: the ctypes binding is generated from it") from e
+        raise FmxError(f"{path} not found: the ctypes binding is generated from it") from e
 
 
 # name -> argtypes of the entry points that return int (0 = ok); the const char* accessors; the argument structs; the integer #defines
 SIGNATURES, ACCESSORS, _structs, CONSTANTS = parse_header(_read_header())
 GemmArgs, AttnArgs, ConvGnArgs = (_structs[_n] for _n in ("fmx_gemm_args", "fmx_attn_args", "fmx_conv_gn_args"))
+# the entry points declared in include/fmx_ext.h (prefix fmxe_; that header says why they are not in fmx.h), bound the same way
+EXT_HEADER = os.path.join(_HERE, "..", "include", "fmx_ext.h")
+EXT_SIGNATURES = parse_header(_read_header(EXT_HEADER), prefix="fmxe_", known_structs=_structs)[0]
 
 
 def source_tree_hash():
@@ -199,7 +204,7 @@ def lib():
             raise FmxError(f"{LIB_PATH} not found: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(hipcc --offload-arch=gfx950).  There is no CPU/PyTorch fallback by design.")
         handle = C.CDLL(LIB_PATH)
-        for name, argtypes, restype in [(n, a, C.c_int) for n, a in SIGNATURES.items()] + [(n, [], C.c_char_p) for n in ACCESSORS]:
+        for name, argtypes, restype in [(n, a, C.c_int) for n, a in {**SIGNATURES, **EXT_SIGNATURES}.items()] + [(n, [], C.c_char_p) for n in ACCESSORS]:
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:

@@ -10,6 +10,7 @@ import torch
 from ... import hipops as ops
 from ...runtime import HipGraph
 from ..patcher.kohya_hrfix import shrink_for_step, shrink_graph_key
+from ..patcher.stylealign import OPTION as STYLEALIGN, group_size_of_call, share_for_call, share_graph_key
 
 
 class SigmaInfo:
@@ -88,7 +89,7 @@ class KModel:
         return entries
 
     def _forward_static(self, key, x, sigma_dev, sig_host, reps, ctxc, control=None, transformer_options=None, c_concat=None, control_plan=None,
-                        freeu=None, shrink=None, pag_from=None):
+                        freeu=None, shrink=None, pag_from=None, share=None):
         """pack -> [ControlNets ->] UNet -> (returns eps view); static buffers per shape so the chain can be graph-replayed.
         `reps`: the stacked copies of the batch: 1, 2 ([uncond ; cond]) or, with the perturbed group of native Perturbed-Attention Guidance
         behind them, 2 or 3; `pag_from`: the first image of that group (backend/nn/unet.py), or None.  Such a call arrives with ("pag",) in `key`,
@@ -98,7 +99,12 @@ class KModel:
         are two graphs.
         `shrink`: the job's native Kohya HRFix parameters (transformer_options["kohya_hrfix"], backend/patcher/kohya_hrfix.py) when this step's
         host sigma lies inside their window, else None.  A shrunk forward launches other kernels on other shapes, so it is part of the graph
-        key as well; a step outside the window replays the plain graph."""
+        key as well; a step outside the window replays the plain graph.
+        `share`: the call's native StyleAlign (transformer_options["stylealign"], backend/patcher/stylealign.py: images per group, mode, strength)
+        or None.  Such a call arrives with ("stylealign", mode, strength) in `key`: other attention launches, and the blend weights are launch
+        arguments, so its static buffers and its graph are its own."""
+        if share is not None and self.diffusion_model._hooks(transformer_options) is not None:     # refused before any launch
+            raise NotImplementedError("StyleAlign (native) together with Python block hooks in transformer_options")
         if pag_from is not None:     # refused before any launch
             if shrink is not None:
                 raise NotImplementedError("Perturbed-Attention Guidance and Kohya HRFix on the same step: the degraded pass of the reference runs "
@@ -136,7 +142,7 @@ class KModel:
         if not self.use_graph or control is not None or hooks is not None:
             # Python hooks cannot be captured, and a ControlNet chain that needs Python per step arrives here with its residuals: eager
             return net.forward_packed(st["xcol"], st["t"], ctxc, bu, hh, ww, control, hooks, concat_term, freeu=freeu, shrink=shrink,
-                                      pag_from=pag_from)
+                                      pag_from=pag_from, share=share)
         active = [e for e in control_plan if e["active"]] if control_plan else []
         gkey = key if not active else key + ("control",) + tuple(e["cm"].exec_serial for e in active)
         if freeu is not None:
@@ -153,7 +159,7 @@ class KModel:
                 outs = e["cm"].forward_static(st["xcol"], st["t"], e["ctxc"], bu, hh, ww, e["gh"])
                 ctrl = e["cn"].control_merge(None, outs, ctrl, torch.float32)
             return net.forward_packed(st["xcol"], st["t"], ctxc, bu, hh, ww, control=ctrl, concat_term=concat_term, freeu=freeu, shrink=shrink,
-                                      pag_from=pag_from)
+                                      pag_from=pag_from, share=share)
 
         def validity():
             # What a captured graph points at: the executors' arenas (re-allocated when a larger shape comes through, e.g. the hires pass),
@@ -226,6 +232,9 @@ class KModel:
         reps = 1 if uncond_ctx is None else 2
         job_options = transformer_options
         freeu = (transformer_options or {}).get("freeu_v2")   # native, no Python hook: stays on the graph path
+        share = share_for_call(transformer_options, b)        # native StyleAlign: the `reps` row groups of b images each
+        if share is not None and self.diffusion_model._hooks(transformer_options) is not None:
+            raise NotImplementedError("StyleAlign (native) together with Python block hooks in transformer_options")
         if self.diffusion_model._hooks(transformer_options) is not None or control_model is not None:
             to = dict(transformer_options or {})
             cond_or_uncond = [1, 0] if reps == 2 else [0]          # batch order [uncond ; cond] (sampling_function.py:187-229)
@@ -245,7 +254,7 @@ class KModel:
         else:
             ctx = cond_ctx
         ctxc = self.diffusion_model.prepare_context(ctx[0], ctx[1])
-        key = (b, c, hh, ww, reps)
+        key = (b, c, hh, ww, reps) if share is None else (b, c, hh, ww, reps) + share_graph_key(share)
         control, plan = None, None
         if control_model is not None:
             # sampling_function.py:261-268: every ControlNet of the chain sees the per-call options, then one get_control on the stacked batch
@@ -261,7 +270,7 @@ class KModel:
                 t_all.fmx_sigma = SigmaInfo(list(sig_host) * reps)
                 control = control_model.get_control(torch.cat([x] * reps), t_all, {"c_crossattn": ctx[0], "y": ctx[1]}, reps)
         eps = self._forward_static(key, x, sigma, sig_host, reps, ctxc, control=control, transformer_options=transformer_options, c_concat=c_concat,
-                                   control_plan=plan, freeu=freeu, shrink=shrink)
+                                   control_plan=plan, freeu=freeu, shrink=shrink, share=share)
         cond_pred = torch.empty_like(x) if want_parts else None
         uncond_pred = torch.empty_like(x) if want_parts else None
         den = ops.cfg_combine(eps, eps.shape[-1], x, sigma, reps, cond_scale, None, cond_pred, uncond_pred,
@@ -287,9 +296,10 @@ class KModel:
         groups = 3 if has_uncond else 2
         ctx = self._stack_ctx_pag(uncond_ctx, cond_ctx)
         ctxc = self.diffusion_model.prepare_context(ctx[0], ctx[1])
-        key = (b, c, hh, ww, groups - 1, "pag")
+        share = share_for_call(transformer_options, b)        # native StyleAlign: the perturbed group is one more share group outside the middle
+        key = (b, c, hh, ww, groups - 1, "pag") if share is None else (b, c, hh, ww, groups - 1, "pag") + share_graph_key(share)
         eps = self._forward_static(key, x, sigma, sig_host, groups, ctxc, c_concat=c_concat, freeu=(transformer_options or {}).get("freeu_v2"),
-                                   pag_from=(groups - 1) * b)
+                                   pag_from=(groups - 1) * b, share=share)
         cond_pred = torch.empty_like(x) if want_parts else None
         uncond_pred = torch.empty_like(x) if want_parts else None
         degraded = torch.empty_like(x) if want_parts else None
@@ -335,13 +345,21 @@ class KModel:
 
     def apply_model(self, x, t, c_concat=None, c_crossattn=None, control=None, transformer_options=None, y=None, **kwargs):
         """Reference signature (k_model.py:25): x fp32 [Bu,C,H,W], t = sigma [Bu] -> denoised fp32."""
+        share = None
+        if (transformer_options or {}).get(STYLEALIGN) is not None:
+            # native StyleAlign: the groups are the entries of cond_or_uncond; refused before any launch when they are unknown or repeat
+            share = share_for_call(transformer_options, group_size_of_call(transformer_options, x.shape[0]))
+            if share is not None and self.diffusion_model._hooks(transformer_options) is not None:
+                raise NotImplementedError("StyleAlign (native) together with Python block hooks in transformer_options")
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
         sigma = t.to(device=self.device, dtype=torch.float32).contiguous()
         ctxc = self.diffusion_model.prepare_context(c_crossattn, y)
         b, c, hh, ww = x.shape
         sig_host = host_sigmas(t)
-        eps = self._forward_static((b, c, hh, ww, 1, "apply"), x, sigma, sig_host, 1, ctxc, control, transformer_options, c_concat,
-                                   freeu=(transformer_options or {}).get("freeu_v2"), shrink=shrink_for_step(transformer_options, sig_host))
+        key = (b, c, hh, ww, 1, "apply") if share is None else (b, c, hh, ww, 1, "apply") + share_graph_key(share)
+        eps = self._forward_static(key, x, sigma, sig_host, 1, ctxc, control, transformer_options, c_concat,
+                                   freeu=(transformer_options or {}).get("freeu_v2"), shrink=shrink_for_step(transformer_options, sig_host),
+                                   share=share)
         return ops.cfg_combine(eps, eps.shape[-1], x, sigma, 1, 1.0, prediction_type=self.predictor.prediction_type,
                                sigma_data=self.predictor.sigma_data)
 
@@ -367,6 +385,8 @@ class KModelFlux:
             raise NotImplementedError("FreeU: UNet models only")   # the reference's script declines models without model_channels
         if (transformer_options or {}).get("kohya_hrfix") is not None:
             raise NotImplementedError("Kohya HRFix: UNet models only")
+        if (transformer_options or {}).get("stylealign") is not None:
+            raise NotImplementedError("StyleAlign: UNet models only")
         if c_concat is not None or control is not None:
             raise NotImplementedError("c_concat / control are outside the txt2img hot path")
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
@@ -383,6 +403,8 @@ class KModelFlux:
             raise NotImplementedError("FreeU: UNet models only")
         if to.get("kohya_hrfix") is not None:
             raise NotImplementedError("Kohya HRFix: UNet models only")
+        if to.get("stylealign") is not None:
+            raise NotImplementedError("StyleAlign: UNet models only")
         if control_model is not None or to.get("patches") or to.get("patches_replace") or to.get("block_modifiers"):
             raise NotImplementedError("ControlNet / per-block hooks are built for the LDM UNet executor, not for the Flux transformer")
         ctx, y, guidance = cond_ctx

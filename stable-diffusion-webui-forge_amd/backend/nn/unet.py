@@ -388,10 +388,44 @@ class IntegratedUNet2DConditionModel:
         ops.attention(qk, qk[:, hd:], vt, batch=pag_from, out=o, **kw)
         return ops.attn_value_rows(vt, o, first=pag_from, count=bu - pag_from, n=n, hd=hd, vt_bs=npad, vt_ds=m_pad)
 
-    def _attn_block(self, b, L, h, bu, n, ctxc, arena, rs1=None, want_next=False, pag_from=None):
+    def _shared_attention(self, qk, vt, bu, n, tpad, H, d, share, pag_from, fill_v):
+        """O [Bu * n, H * dp] of attn1 under native StyleAlign: every group of share.b consecutive images is ONE sequence of T = b * n tokens, which
+        it already is in the [Q | K] rows and the V^T columns -- the same kernel with batch = groups and the strides of a group, no copy and no
+        mask.  `tpad` rows / columns per group in both operands (= T unless T is ragged: the group-padded layout of _attn_block).  O comes out
+        dense.  pag_from: the groups from that image on get no attention; fill_v: they get their V instead (see _self_attention)."""
+        dp = _dpad(d)
+        hd = H * dp
+        gb = share.b
+        t_seq = gb * n
+        cols = (bu // gb) * tpad
+        lim = bu if pag_from is None else pag_from
+        o = ops.empty((bu * n, hd))
+        ops.attention(qk, qk[:, hd:], vt, batch=lim // gb, heads=H, nq=t_seq, nk=t_seq, nk_pad=tpad, dpad=dp, scale=d ** -0.5, q_bs=tpad * 2 * hd,
+                      q_rs=2 * hd, k_bs=tpad * 2 * hd, k_rs=2 * hd, vt_bs=tpad, vt_hs=dp * cols, vt_ds=cols, out=o, o_bs=t_seq * hd)
+        if fill_v:
+            for g in range(lim // gb, bu // gb):    # image j of group g: the columns g * tpad + j * n ... of V^T, the rows (g * b + j) * n ... of O
+                ops.attn_value_rows(vt[:, g * tpad:], o[g * t_seq:], first=0, count=gb, n=n, hd=hd, vt_bs=n, vt_ds=cols)
+        return o
+
+    def _pad_buf(self, key, shape):
+        """persistent zero-filled LayerNorm output for ragged token counts (see _attn_block); bounded, and captured graphs that point at a dropped
+        buffer are invalidated via the epoch"""
+        padbuf = self._pad_bufs.get(key)
+        if padbuf is None:
+            if len(self._pad_bufs) >= 24:
+                torch.cuda.synchronize(self.device)
+                self._pad_bufs.clear()
+                self.arena_epoch += 1
+            padbuf = self._pad_bufs[key] = torch.zeros(*shape, dtype=torch.float16, device=self.device)
+        return padbuf
+
+    def _attn_block(self, b, L, h, bu, n, ctxc, arena, rs1=None, want_next=False, pag_from=None, share=None):
         """One BasicTransformerBlock on h [M, C] (updated in place).  rs1: the row statistics the projection that WROTE h left (proj_in or the
         previous block's ff.net.2) -- norm1 then runs folded into the q|k and V^T projections; want_next: leave the statistics of this block's
         output for the next block's norm1.  pag_from: see _self_attention (everything but the attention itself runs on all rows).
+        share: None, or native StyleAlign (backend/patcher/stylealign.py Share): the self-attention of every group of share.b images runs over
+        their joined tokens ("aligned"), or is blended with the ordinary one ("blend", ops.attn_blend); see _shared_attention.  What governs the
+        projections is then the token count of a group, T = b * n: tile-aligned T runs them dense (and folded) even where n alone is ragged.
         -> that RowStats (or None)."""
         H, d = L.heads, L.dim_head
         dp = _dpad(d)
@@ -404,42 +438,63 @@ class IntegratedUNet2DConditionModel:
         rs_next = ops.RowStats(m_tok, h.shape[1]) if (want_next and fold) else None
         mk = arena.mark()
         # self attention
-        folded1 = n % 64 == 0 and rs1 is not None and bool(rs1.parts) and (b + ".attn1.v.ln") in self.w
-        if folded1:
-            wqk, csqk, bqk = self.w[b + ".attn1.qk.ln"]
-            ab = ops.empty((m_tok, 2), torch.float32)     # {rstd, -mean rstd} per token: the q|k GEMM derives them anyway and leaves them for V^T
-            qk = ops.conv_gemm(h, wqk, wqk.shape[0], bias=bqk, ln=(rs1, csqk, 1e-5), ln_ab_out=ab)   # [M, 2*H*dp] = [Q | K] of LN(h)
-            wvf, vcb = self.w[b + ".attn1.v.ln"]
-            vt = ops.conv_gemm(wvf, h, m_tok, ln_swapped=(ab, vcb))                                   # [H*dp, M] = V^T of LN(h)
+        seq = n if share is None else share.b * n      # tokens per attention sequence: an image, or a StyleAlign group
+        own = share is None or share.mode == "blend"   # the ordinary per-image attention is wanted (into o)
+        aligned = share is not None and share.mode == "aligned"
+        o = sh = None
+        folded1 = seq % 64 == 0 and rs1 is not None and bool(rs1.parts) and (b + ".attn1.v.ln") in self.w
+        if seq % 64 == 0:
+            if folded1:
+                wqk, csqk, bqk = self.w[b + ".attn1.qk.ln"]
+                ab = ops.empty((m_tok, 2), torch.float32)     # {rstd, -mean rstd} per token: the q|k GEMM derives them anyway and leaves them for V^T
+                qk = ops.conv_gemm(h, wqk, wqk.shape[0], bias=bqk, ln=(rs1, csqk, 1e-5), ln_ab_out=ab)   # [M, 2*H*dp] = [Q | K] of LN(h)
+                wvf, vcb = self.w[b + ".attn1.v.ln"]
+                vt = ops.conv_gemm(wvf, h, m_tok, ln_swapped=(ab, vcb))                                   # [H*dp, M] = V^T of LN(h)
+            else:
+                n1 = ops.layernorm(h, *self.w[b + ".norm1"])
+                qk = ops.linear(n1, self.w[b + ".attn1.qk"])                   # [M, 2*H*dp] = [Q | K]
+                vt = ops.conv_gemm(self.w[b + ".attn1.v"], n1, m_tok)          # [H*dp, M] = V^T (operand swap)
             self._tap_qkv(b + ".attn1", qk[:, :hd].view(bu, n, hd), qk[:, hd:].view(bu, n, hd), vt.view(hd, bu, n))
-            o = self._self_attention(qk, vt, bu, n, n, H, d, pag_from)
-        elif n % 64 == 0:
-            n1 = ops.layernorm(h, *self.w[b + ".norm1"])
-            qk = ops.linear(n1, self.w[b + ".attn1.qk"])                   # [M, 2*H*dp] = [Q | K]
-            vt = ops.conv_gemm(self.w[b + ".attn1.v"], n1, m_tok)          # [H*dp, M] = V^T (operand swap)
-            self._tap_qkv(b + ".attn1", qk[:, :hd].view(bu, n, hd), qk[:, hd:].view(bu, n, hd), vt.view(hd, bu, n))
-            o = self._self_attention(qk, vt, bu, n, n, H, d, pag_from)
-        else:
+            if own and n % 64 == 0:
+                o = self._self_attention(qk, vt, bu, n, n, H, d, pag_from)
+            if share is not None:
+                # the projections ran over dense [Bu * n] rows as ever: only the attention call changes
+                sh = self._shared_attention(qk, vt, bu, n, seq, H, d, share, pag_from, fill_v=aligned and pag_from is not None)
+        if own and n % 64 != 0:
             # ragged token count (latent H*W not a multiple of the 64-key tile, e.g. SDXL at 832x1216): LayerNorm writes each image's tokens
             # at a padded stride into a persistent zero-filled buffer, so Q|K and V^T are still ONE batched GEMM each over [Bu * n_pad]
             # rows; the pad rows are zeros in, zeros out (no bias on q / k / v) and masked by nk in the attention kernel
             npad = -(-n // 64) * 64
-            key = (bu, npad, h.shape[1])
-            padbuf = self._pad_bufs.get(key)
-            if padbuf is None:
-                if len(self._pad_bufs) >= 24:   # bounded; captured graphs that point at the dropped buffers are invalidated via the epoch
-                    torch.cuda.synchronize(self.device)
-                    self._pad_bufs.clear()
-                    self.arena_epoch += 1
-                padbuf = self._pad_bufs[key] = torch.zeros(bu, npad, h.shape[1], dtype=torch.float16, device=self.device)
+            padbuf = self._pad_buf((bu, npad, h.shape[1]), (bu, npad, h.shape[1]))
             ops.layernorm_padded(h, *self.w[b + ".norm1"], out=padbuf, rows_per_image=n)
             p2d = padbuf.view(bu * npad, -1)
             qk = ops.linear(p2d, self.w[b + ".attn1.qk"])                  # [Bu*n_pad, 2*H*dp]
             vt = ops.conv_gemm(self.w[b + ".attn1.v"], p2d, bu * npad)     # [H*dp, Bu*n_pad]
-            if pag_from is not None:
+            if pag_from is not None or (share is not None and seq % 64 != 0):
                 self._tap_qkv(b + ".attn1", qk[:, :hd].view(bu, npad, hd)[:, :n], qk[:, hd:].view(bu, npad, hd)[:, :n],
                               vt.view(hd, bu, npad)[:, :, :n])
             o = self._self_attention(qk, vt, bu, n, npad, H, d, pag_from)
+        if share is not None and seq % 64 != 0:
+            # ragged group: the same padding per GROUP -- LayerNorm writes each group's b * n tokens at a padded stride, one q|k and one V^T GEMM
+            # over [groups * pad64(T)] rows, and O comes out dense.  (Under "blend" the ordinary attention above keeps its per-image layout, with
+            # its own LayerNorm and projections: deriving both from one set needs n % 8 == 0 and spare tiles.)
+            seqs, tpad = bu // share.b, -(-seq // 64) * 64
+            padbuf = self._pad_buf(("group", seqs, tpad, h.shape[1], seq), (seqs, tpad, h.shape[1]))
+            ops.layernorm_padded(h, *self.w[b + ".norm1"], out=padbuf, rows_per_image=seq)
+            p2d = padbuf.view(seqs * tpad, -1)
+            qk = ops.linear(p2d, self.w[b + ".attn1.qk"])                  # [groups*T_pad, 2*H*dp]
+            vt = ops.conv_gemm(self.w[b + ".attn1.v"], p2d, seqs * tpad)   # [H*dp, groups*T_pad]
+            if aligned and self.tap is not None:
+                # the tap reports per-image operands of n tokens; out of the group-padded buffers they are no single view: copies, tap runs only
+                self._tap_qkv(b + ".attn1", qk[:, :hd].view(seqs, tpad, hd)[:, :seq].reshape(bu, n, hd),
+                              qk[:, hd:].view(seqs, tpad, hd)[:, :seq].reshape(bu, n, hd), vt.view(hd, seqs, tpad)[:, :, :seq].reshape(hd, bu, n))
+            sh = self._shared_attention(qk, vt, bu, n, tpad, H, d, share, pag_from, fill_v=aligned and pag_from is not None)
+        if aligned:
+            o = sh
+        elif share is not None:
+            # (1.0 - strength) * own + strength * shared with the reference's roundings; the perturbed images of Perturbed-Attention Guidance keep V
+            rows = (bu if pag_from is None else pag_from) * n
+            ops.attn_blend(o[:rows], sh[:rows], share.strength, out=o[:rows])
         self._tap(b + ".attn1.o", o.view(bu, n, -1))
         ops.linear(o, *self.w[b + ".attn1.out"], residual=h, out=h, ld_out=h.shape[1], row_stats=rs2)
         arena.release(mk)
@@ -579,7 +634,7 @@ class IntegratedUNet2DConditionModel:
             return h
         return r.permute(0, 2, 3, 1).to(torch.float16).contiguous()
 
-    def _spatial_transformer(self, L, x, ctxc, arena, to=None, pag_from=None):
+    def _spatial_transformer(self, L, x, ctxc, arena, to=None, pag_from=None, share=None):
         k = L.key
         bu, hh, ww, c = x.shape
         n = hh * ww
@@ -592,7 +647,8 @@ class IntegratedUNet2DConditionModel:
         if hooked and pag_from is not None:
             raise NotImplementedError("Perturbed-Attention Guidance (native) together with Python transformer patches")
         # norm1 of every block folded into its q|k / V^T projections: the GEMM that writes h (proj_in, then each block's ff.net.2) leaves the row sums
-        fold1 = _LN_FOLD and _LN_FOLD1 and not hooked and n % 64 == 0 and (f"{k}.transformer_blocks.0.attn1.v.ln") in self.w
+        # (under native StyleAlign the attention sequence is a group's b * n tokens: that count decides, as in _attn_block)
+        fold1 = _LN_FOLD and _LN_FOLD1 and not hooked and (n if share is None else share.b * n) % 64 == 0 and (f"{k}.transformer_blocks.0.attn1.v.ln") in self.w
         rs1 = ops.RowStats(bu * n, inner) if fold1 else None
         h = ops.linear(g.view(-1, c), *self.w[k + ".proj_in"], row_stats=rs1)  # 1x1 conv == Linear in NHWC
         self._tap(k + ".proj_in", h.view(bu, n, -1))
@@ -602,7 +658,7 @@ class IntegratedUNet2DConditionModel:
                 self._attn_block_hooked(f"{k}.transformer_blocks.{di}", L, h, bu, n, ctxc, arena, to)
             else:
                 rs1 = self._attn_block(f"{k}.transformer_blocks.{di}", L, h, bu, n, ctxc, arena, rs1=rs1, want_next=fold1 and di + 1 < L.depth,
-                                       pag_from=pag_from)
+                                       pag_from=pag_from, share=share)
             self._tap(f"{k}.transformer_blocks.{di}", h.view(bu, n, -1))
         _, st = ops.linear(h, *self.w[k + ".proj_out"], residual=x.view(-1, c), out=out.view(-1, c), ld_out=c, n=bu, h=hh, w=ww, stats=True,
                            stats_partial=out_part)
@@ -631,7 +687,7 @@ class IntegratedUNet2DConditionModel:
             return Upsample(key=L.key)
         return Conv2d(key=L.key)
 
-    def _run_block(self, blk, h, skip, emb_all, ctxc, arena, up_to=None, to=None, pag_from=None):
+    def _run_block(self, blk, h, skip, emb_all, ctxc, arena, up_to=None, to=None, pag_from=None, share=None):
         inner = to.get("block_inner_modifiers", []) if to is not None else []
         wrapper = to.get("group_norm_wrapper") if to is not None else None
         standins = TimestepEmbedSequential(self._layer_standin(L) for L in blk) if inner else None
@@ -653,7 +709,7 @@ class IntegratedUNet2DConditionModel:
                 h = self._res(L, h, skip, emb_all, arena)
                 skip = None
             elif isinstance(L, SpatialT):
-                h = self._spatial_transformer(L, h, ctxc, arena, to, pag_from)
+                h = self._spatial_transformer(L, h, ctxc, arena, to, pag_from, share)
                 if to is not None and "transformer_index" in to:
                     to["transformer_index"] += 1  # unet.py:82-84
             elif isinstance(L, Down):
@@ -726,7 +782,8 @@ class IntegratedUNet2DConditionModel:
         self._concat_cache = (key, term, c_concat)
         return term
 
-    def _forward_impl(self, xcol, t, ctxc, bu, hh, ww, arena, control=None, to=None, concat_term=None, freeu=None, shrink=None, pag_from=None):
+    def _forward_impl(self, xcol, t, ctxc, bu, hh, ww, arena, control=None, to=None, concat_term=None, freeu=None, shrink=None, pag_from=None,
+                      share=None):
         """xcol: [Bu*H*W, 64] im2col of the (scaled) input; t: [Bu] fp32 table indices.  -> eps [Bu*H*W, out_ch].
         `to`: transformer_options with Python hooks (unet.py:696-763 hook points), or None on the fast path.
         `freeu`: a FreeUParams tuple (b1, b2, s1, s2, ...) of backend/patcher/freeu.py, or None: native FreeU v2 on the inputs of the
@@ -741,7 +798,18 @@ class IntegratedUNet2DConditionModel:
         `pag_from`: None, or the first image of the perturbed group of native Perturbed-Attention Guidance (backend/patcher/pag.py; KModel stacks
         [uncond ; cond ; cond] and hands over 2b, or b without uncond).  The images from there on get V as the self-attention output of EVERY
         transformer block of the middle block -- the reference's patches_replace key ("middle", 0) carries no block index, so it matches all of
-        them (attention.py / unet.py:201-214) -- and run like the others everywhere else.  Fast path, captured graph."""
+        them (attention.py / unet.py:201-214) -- and run like the others everywhere else.  Fast path, captured graph.
+        `share`: None, or native StyleAlign (backend/patcher/stylealign.py Share(b, mode, strength); KModel hands it over for groups of b > 1 images):
+        in EVERY transformer block of every level the self-attention of each group of b consecutive images runs over the group's joined tokens
+        (the reference's set_model_replace_all(attn1_proc, "attn1")); attn2 is untouched.  With `pag_from` the perturbed group keeps V in the middle
+        block (the degraded pass replaces ("middle", 0) itself) and is one more group everywhere else.  Fast path, captured graph."""
+        if share is not None:
+            if share.b < 2 or bu % share.b != 0 or (pag_from is not None and pag_from % share.b != 0):
+                raise ValueError(f"StyleAlign groups of {share.b} images do not tile the batch of {bu} (perturbed group from {pag_from})")
+            if share.mode not in ("aligned", "blend"):
+                raise ValueError(f"StyleAlign mode {share.mode!r}")
+            if to is not None:
+                raise NotImplementedError("StyleAlign (native) together with Python block hooks in transformer_options")
         if pag_from is not None:
             if not 0 < pag_from < bu:
                 raise ValueError(f"pag_from {pag_from} outside the batch of {bu}")
@@ -810,7 +878,7 @@ class IntegratedUNet2DConditionModel:
                     h = self._call_nchw(m, h, "after", conv_in[0], 0, conv_in, to)
             else:
                 h = modify(h, "before")
-                h = self._run_block(blk, h, None, emb_all, ctxc, arena, to=to)
+                h = self._run_block(blk, h, None, emb_all, ctxc, arena, to=to, share=share)
             h = self._apply_control(h, control, "input")
             h = modify(h, "after")
             if shrink is not None and bi == shrink.block_number and not shrink.downscale_after_skip:
@@ -825,7 +893,7 @@ class IntegratedUNet2DConditionModel:
         if to is not None:
             to["block"] = ("middle", 0)
         h = modify(h, "before")
-        h = self._run_block(lay.middle, h, None, emb_all, ctxc, arena, to=to, pag_from=pag_from)
+        h = self._run_block(lay.middle, h, None, emb_all, ctxc, arena, to=to, pag_from=pag_from, share=share)
         h = self._apply_control(h, control, "middle")
         h = modify(h, "after")
         for bi, blk in enumerate(lay.output_blocks):
@@ -855,7 +923,7 @@ class IntegratedUNet2DConditionModel:
                 # halves separate (dual-input GroupNorm / conv), so it is materialised only when a modifier wants to see it
                 cat = modify(torch.cat([h, skip], dim=-1), "before")
                 h, skip = cat[..., :h.shape[-1]].contiguous(), cat[..., h.shape[-1]:].contiguous()
-            h = self._run_block(blk, h, skip, emb_all, ctxc, arena, up_to, to=to)
+            h = self._run_block(blk, h, skip, emb_all, ctxc, arena, up_to, to=to, share=share)
             h = modify(h, "after")
         if to is not None:
             to["block"] = ("last", 0)
@@ -900,17 +968,17 @@ class IntegratedUNet2DConditionModel:
         return self._arena
 
     def forward_packed(self, xcol, t, ctxc, bu, hh, ww, control=None, transformer_options=None, concat_term=None, freeu=None, shrink=None,
-                       pag_from=None):
+                       pag_from=None, share=None):
         """Hot-path entry (no layout conversion): returns eps as fp16 [Bu*H*W, out_channels] living in the arena
         (valid until the next forward).  `freeu`, `shrink`: see _forward_impl (the caller takes them out of transformer_options["freeu_v2"] /
-        ["kohya_hrfix"]); `pag_from`: see _forward_impl."""
+        ["kohya_hrfix"]); `pag_from`, `share`: see _forward_impl."""
         while True:
             arena = self._get_arena(bu, hh, ww)
             arena.reset()
             try:
                 with arena:
                     return self._forward_impl(xcol, t, ctxc, bu, hh, ww, arena, control, self._hooks(transformer_options), concat_term, freeu,
-                                              shrink, pag_from)
+                                              shrink, pag_from, share)
             except ArenaOverflow:
                 torch.cuda.synchronize(self.device)
                 self._arena_bytes = arena.capacity * 2

@@ -30,6 +30,14 @@ def shard_range(total, rank, world_size):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
+def check_batch_coupled_options(model_options, world_size):
+    """Images of a batch are independent -- except under a model option that couples them.  Native StyleAlign (backend/patcher/stylealign.py)
+    shares self-attention among the images of a batch, so a batch split over more than one rank would shrink its groups: NotImplementedError,
+    raised by the sharded entry on every rank before any collective."""
+    from .backend.patcher.stylealign import check_world
+    check_world((model_options or {}).get("transformer_options"), world_size)
+
+
 def _flatten(cond):
     if isinstance(cond, dict):
         keys = sorted(cond.keys())

@@ -856,6 +856,19 @@ def attn_value_rows(vt, out, *, first, count, n, hd, vt_bs, vt_ds, o_bs=None):
     return out
 
 
+def attn_blend(own, shared, strength, out=None):
+    """(1.0 - strength) * own + strength * shared on fp16 tensors, with the roundings of that torch expression (include/fmx_ext.h, section
+    "StyleAlign"): the blend of StyleAlign's own and batch-shared self-attention outputs.  own / shared: contiguous, one shape; out: None (a new
+    tensor), or a contiguous tensor of that shape, own and shared included.  The weights are made as the reference makes them: the subtraction
+    in Python's double, both then as fp32 launch arguments."""
+    _check_f16(own, shared, out)
+    if out is None:
+        out = empty(own.shape, torch.float16, own.device)
+    assert own.shape == shared.shape == out.shape and own.is_contiguous() and shared.is_contiguous() and out.is_contiguous()
+    _call("fmxe_attn_blend_f16", _p(own), _p(shared), _p(out), float(1.0 - float(strength)), float(strength), own.numel())
+    return out
+
+
 def euler_step(x, denoised, sigma, sigma_next, noise=None, noise_scale=0.0, out=None):
     if out is None:
         out = torch.empty_like(x)

@@ -429,6 +429,11 @@ def process_images_sharded(p, gather_images=True, dst=0) -> Processed:
     rank, ws = fdist.world()
     if not fdist.group_active():
         return process_images(p)
+    # a model option that couples the images of a batch cannot be sharded: refused on every rank (each holds the patcher), before any collective.
+    # The patcher the job samples with is forge_objects_after_applying_lora.unet -- sample() copies that set over forge_objects just before
+    # sampling -- so that one is checked, and forge_objects.unet as well, which a script may have patched in place
+    for objs in (getattr(p.sd_model, "forge_objects_after_applying_lora", None), getattr(p.sd_model, "forge_objects", None)):
+        fdist.check_batch_coupled_options(getattr(getattr(objs, "unet", None), "model_options", None), ws)
     dev = p.sd_model.device
     B, total = p.batch_size, p.batch_size * p.n_iter
     # ---- 1. job header + conditioning from the owner.  Everything that can fail on the owner BEFORE the first collective (prompt encoding, the

@@ -12,6 +12,8 @@ batch sizes -- and what they cost.
     python tools/bench_features.py --only pag        Perturbed-Attention Guidance: plain / native (third group of rows in the captured graph) / the same
                                                      arithmetic as a Python post-CFG function with an attn1 replace patch (a second, eager model call),
                                                      interleaved in one process, device events around every job
+    python tools/bench_features.py --only stylealign StyleAlign: plain / native at strength 1.0 and 0.5 (captured graph) / the reference's attn1 replace
+                                                    patch at both strengths on the hooked executor, timed alternately in one process
     python tools/bench_features.py --only taesd      the TAESD decode of batch x (res/8)^2 SDXL-shaped latents (synthetic weights, fp16) next to the Full
                                                      VAE decode of the same latents in the same process: median of 5 after warm-up, events around the calls
 """
@@ -408,8 +410,59 @@ def main():
                           "copy_kernels_share_of_native_step": round(len(per_call) * copy_ms / med["pag_native"], 5),
                           "finite": finite, "shape": list(lat.shape)}), flush=True)
 
+    def stylealign_leg(rounds=3):
+        """Plain, native StyleAlign (transformer option: the self-attention of each CFG group over its joined tokens, captured graph) at strength 1.0
+        and 0.5, and the same patch as the reference script installs it (tests/stylealign_refs.py: an attn1 replace patch on every block, on the
+        eager hooked executor) at both strengths -- primed once each, then timed alternately, `rounds` jobs of a.steps steps per route in this one
+        process, device events around each job.  native 0.5 minus native 1.0 is what the ordinary attention launches plus the blend add to a
+        blended step: the number a fused single-pass kernel would be judged against."""
+        import stylealign_refs as sr
+        from forge_amd.backend.patcher.stylealign import patch_stylealign
+        base = eng.forge_objects.unet
+        variants = {"plain": None, "stylealign_native_1.0": patch_stylealign(base, 1.0), "stylealign_native_0.5": patch_stylealign(base, 0.5),
+                    "stylealign_python_1.0": sr.python_stylealign(base, 1.0), "stylealign_python_0.5": sr.python_stylealign(base, 0.5)}
+        saved = eng.forge_objects_after_applying_lora
+
+        def once(unet, n):
+            if unet is not None:
+                eng.forge_objects_after_applying_lora = saved.shallow_copy()
+                eng.forge_objects_after_applying_lora.unet = unet
+            try:
+                pr = processing.StableDiffusionProcessingTxt2Img(sd_model=eng, c=c1, uc=u1, seed=1, sampler_name="Euler", batch_size=b, steps=n,
+                                                                 cfg_scale=7.0, width=width, height=height, do_decode=False)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                lat = processing.process_images(pr).latents
+                e1.record()
+                torch.cuda.synchronize()
+                return e0.elapsed_time(e1), lat
+            finally:
+                eng.forge_objects_after_applying_lora = saved
+                eng.forge_objects = saved.shallow_copy()
+        for unet in variants.values():    # priming (arena, caches, graphs)
+            once(unet, 4)
+        ms = {k: [] for k in variants}
+        finite = True
+        for _ in range(rounds):
+            for k, unet in variants.items():
+                once(unet, 2)             # a job on another route came before: what follows a change of route is not timed
+                dt, lat = once(unet, a.steps)
+                ms[k].append(round(dt / a.steps, 2))
+                finite = finite and bool(torch.isfinite(lat).all())
+        med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+        print(json.dumps({"case": f"StyleAlign (share attention in batch, groups of {b} images): plain vs native (captured graph) vs the Python route "
+                                  "(attn1 replace patch on every block, eager hooked executor)", "sampler": "Euler", "steps": a.steps, "rounds": rounds,
+                          "ms_per_step": med, "ms_per_step_rounds": ms,
+                          "native_over_plain": {s: round(med[f"stylealign_native_{s}"] / med["plain"], 3) for s in ("1.0", "0.5")},
+                          "python_over_native": {s: round(med[f"stylealign_python_{s}"] / med[f"stylealign_native_{s}"], 3) for s in ("1.0", "0.5")},
+                          "own_attention_plus_blend_ms_per_step": round(med["stylealign_native_0.5"] - med["stylealign_native_1.0"], 2),
+                          "finite": finite, "shape": list(lat.shape)}), flush=True)
+
     if "one" in what:
         run(f"{width}x{height}", sampler="Euler")
+    if "stylealign" in what:
+        stylealign_leg()
     if "pag" in what:
         pag_leg()
     if "dynthresh" in what:
