@@ -1,4 +1,4 @@
-"""ctypes binding of libfmx_gfx950.so (C-ABI declared in include/fmx.h; include/fmx_ext.h holds entry points not yet declared there).
+"""ctypes binding of libfmx_gfx950.so (C-ABI declared in include/fmx.h; include/fmx_ext.h and include/fmx_lllite.h hold entry points not yet declared there).
 
 The library is built in-tree by `build()` (hipcc --offload-arch=gfx950) so that it travels with the
 repo snapshot.  There is deliberately NO fallback: if the shared object is missing or a symbol is
@@ -48,6 +48,7 @@ HEADER = os.path.join(_HERE, "..", "include", "fmx.h")
 _SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64,
             "float": C.c_float, "double": C.c_double}
 _STRUCT_NAMES = {"fmx_gemm_args": "GemmArgs", "fmx_attn_args": "AttnArgs", "fmx_conv_gn_args": "ConvGnArgs"}
+_HEADER_OF_PREFIX = {"fmx_": "fmx.h", "fmxe_": "fmx_ext.h", "fmxl_": "fmx_lllite.h"}
 _PARAM = re.compile(r"(?:const )?(\w+) ?((?:\* ?(?:const ?)?)*)(\w+)?")
 
 
@@ -59,7 +60,7 @@ def parse_header(text, prefix="fmx_", known_structs=None):
     `char*` is c_char_p, every other pointer -- and every pointer field of a struct -- c_void_p.  Whatever is left between the declarations and
     does not parse as one of these forms raises FmxError naming the text: nothing is skipped."""
     def bad(what):
-        return FmxError(f"include/{'fmx.h' if prefix == 'fmx_' else 'fmx_ext.h'}: cannot bind {' '.join(what.split())!r}")
+        return FmxError(f"include/{_HEADER_OF_PREFIX.get(prefix, prefix + '*.h')}: cannot bind {' '.join(what.split())!r}")
 
     def scalar(ctype, where):
         if ctype not in _SCALARS:
@@ -138,6 +139,10 @@ GemmArgs, AttnArgs, ConvGnArgs = (_structs[_n] for _n in ("fmx_gemm_args", "fmx_
 # the entry points declared in include/fmx_ext.h (prefix fmxe_; that header says why they are not in fmx.h), bound the same way
 EXT_HEADER = os.path.join(_HERE, "..", "include", "fmx_ext.h")
 EXT_SIGNATURES = parse_header(_read_header(EXT_HEADER), prefix="fmxe_", known_structs=_structs)[0]
+# the ControlNet-LLLite entry point of include/fmx_lllite.h (prefix fmxl_; that header says why it is in neither of the other two) and its slot struct
+LLLITE_HEADER = os.path.join(_HERE, "..", "include", "fmx_lllite.h")
+LLLITE_SIGNATURES, _, _lllite_structs, _ = parse_header(_read_header(LLLITE_HEADER), prefix="fmxl_", known_structs=_structs)
+LlliteSlot = _lllite_structs["fmxl_lllite_slot"]
 
 
 def source_tree_hash():
@@ -204,7 +209,7 @@ def lib():
             raise FmxError(f"{LIB_PATH} not found: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(hipcc --offload-arch=gfx950).  There is no CPU/PyTorch fallback by design.")
         handle = C.CDLL(LIB_PATH)
-        for name, argtypes, restype in [(n, a, C.c_int) for n, a in {**SIGNATURES, **EXT_SIGNATURES}.items()] + [(n, [], C.c_char_p) for n in ACCESSORS]:
+        for name, argtypes, restype in [(n, a, C.c_int) for n, a in {**SIGNATURES, **EXT_SIGNATURES, **LLLITE_SIGNATURES}.items()] + [(n, [], C.c_char_p) for n in ACCESSORS]:
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:

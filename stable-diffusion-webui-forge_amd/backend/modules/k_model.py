@@ -10,6 +10,7 @@ import torch
 from ... import hipops as ops
 from ...runtime import HipGraph
 from ..patcher.kohya_hrfix import shrink_for_step, shrink_graph_key
+from ..patcher.lllite import FEATURE as LLLITE_FEATURE, lllite_for_call, lllite_graph_key, lllite_of
 from ..patcher.stylealign import OPTION as STYLEALIGN, group_size_of_call, share_for_call, share_graph_key
 
 
@@ -89,7 +90,7 @@ class KModel:
         return entries
 
     def _forward_static(self, key, x, sigma_dev, sig_host, reps, ctxc, control=None, transformer_options=None, c_concat=None, control_plan=None,
-                        freeu=None, shrink=None, pag_from=None, share=None):
+                        freeu=None, shrink=None, pag_from=None, share=None, lllite=None):
         """pack -> [ControlNets ->] UNet -> (returns eps view); static buffers per shape so the chain can be graph-replayed.
         `reps`: the stacked copies of the batch: 1, 2 ([uncond ; cond]) or, with the perturbed group of native Perturbed-Attention Guidance
         behind them, 2 or 3; `pag_from`: the first image of that group (backend/nn/unet.py), or None.  Such a call arrives with ("pag",) in `key`,
@@ -102,9 +103,18 @@ class KModel:
         key as well; a step outside the window replays the plain graph.
         `share`: the call's native StyleAlign (transformer_options["stylealign"], backend/patcher/stylealign.py: images per group, mode, strength)
         or None.  Such a call arrives with ("stylealign", mode, strength) in `key`: other attention launches, and the blend weights are launch
-        arguments, so its static buffers and its graph are its own."""
+        arguments, so its static buffers and its graph are its own.
+        `lllite`: the job's native ControlNet-LLLite unit (transformer_options["lllite"], backend/patcher/lllite.py) when this MODEL CALL lies inside
+        its window -- the caller advanced the unit's call counter -- else None.  Such a call arrives with ("lllite", unit, strength) in `key`: the
+        blocks that have modules launch other kernels; a call outside the window is the plain call on the plain graph."""
         if share is not None and self.diffusion_model._hooks(transformer_options) is not None:     # refused before any launch
             raise NotImplementedError("StyleAlign (native) together with Python block hooks in transformer_options")
+        if lllite is not None:     # refused before any launch
+            if self.diffusion_model._hooks(transformer_options) is not None:
+                raise NotImplementedError(f"{LLLITE_FEATURE} (native) together with Python block hooks in transformer_options")
+            if pag_from is not None or share is not None or shrink is not None:
+                raise NotImplementedError(f"{LLLITE_FEATURE} with native Perturbed-Attention Guidance, StyleAlign or Kohya HRFix on the same job")
+            lllite.prepare()       # the cond embeddings, once per unit and outside any capture
         if pag_from is not None:     # refused before any launch
             if shrink is not None:
                 raise NotImplementedError("Perturbed-Attention Guidance and Kohya HRFix on the same step: the degraded pass of the reference runs "
@@ -142,7 +152,7 @@ class KModel:
         if not self.use_graph or control is not None or hooks is not None:
             # Python hooks cannot be captured, and a ControlNet chain that needs Python per step arrives here with its residuals: eager
             return net.forward_packed(st["xcol"], st["t"], ctxc, bu, hh, ww, control, hooks, concat_term, freeu=freeu, shrink=shrink,
-                                      pag_from=pag_from, share=share)
+                                      pag_from=pag_from, share=share, lllite=lllite)
         active = [e for e in control_plan if e["active"]] if control_plan else []
         gkey = key if not active else key + ("control",) + tuple(e["cm"].exec_serial for e in active)
         if freeu is not None:
@@ -159,7 +169,7 @@ class KModel:
                 outs = e["cm"].forward_static(st["xcol"], st["t"], e["ctxc"], bu, hh, ww, e["gh"])
                 ctrl = e["cn"].control_merge(None, outs, ctrl, torch.float32)
             return net.forward_packed(st["xcol"], st["t"], ctxc, bu, hh, ww, control=ctrl, concat_term=concat_term, freeu=freeu, shrink=shrink,
-                                      pag_from=pag_from, share=share)
+                                      pag_from=pag_from, share=share, lllite=lllite)
 
         def validity():
             # What a captured graph points at: the executors' arenas (re-allocated when a larger shape comes through, e.g. the hires pass),
@@ -235,6 +245,9 @@ class KModel:
         share = share_for_call(transformer_options, b)        # native StyleAlign: the `reps` row groups of b images each
         if share is not None and self.diffusion_model._hooks(transformer_options) is not None:
             raise NotImplementedError("StyleAlign (native) together with Python block hooks in transformer_options")
+        # native ControlNet-LLLite: the window is tested here, on the host, once per model call (the unit's call counter advances)
+        lllite = lllite_for_call(transformer_options, self.diffusion_model._hooks(transformer_options),
+                                 (("StyleAlign", (transformer_options or {}).get(STYLEALIGN)), ("Kohya HRFix", (transformer_options or {}).get("kohya_hrfix"))))
         if self.diffusion_model._hooks(transformer_options) is not None or control_model is not None:
             to = dict(transformer_options or {})
             cond_or_uncond = [1, 0] if reps == 2 else [0]          # batch order [uncond ; cond] (sampling_function.py:187-229)
@@ -255,6 +268,8 @@ class KModel:
             ctx = cond_ctx
         ctxc = self.diffusion_model.prepare_context(ctx[0], ctx[1])
         key = (b, c, hh, ww, reps) if share is None else (b, c, hh, ww, reps) + share_graph_key(share)
+        if lllite is not None:
+            key = key + lllite_graph_key(lllite)
         control, plan = None, None
         if control_model is not None:
             # sampling_function.py:261-268: every ControlNet of the chain sees the per-call options, then one get_control on the stacked batch
@@ -270,7 +285,7 @@ class KModel:
                 t_all.fmx_sigma = SigmaInfo(list(sig_host) * reps)
                 control = control_model.get_control(torch.cat([x] * reps), t_all, {"c_crossattn": ctx[0], "y": ctx[1]}, reps)
         eps = self._forward_static(key, x, sigma, sig_host, reps, ctxc, control=control, transformer_options=transformer_options, c_concat=c_concat,
-                                   control_plan=plan, freeu=freeu, shrink=shrink, share=share)
+                                   control_plan=plan, freeu=freeu, shrink=shrink, share=share, lllite=lllite)
         cond_pred = torch.empty_like(x) if want_parts else None
         uncond_pred = torch.empty_like(x) if want_parts else None
         den = ops.cfg_combine(eps, eps.shape[-1], x, sigma, reps, cond_scale, None, cond_pred, uncond_pred,
@@ -283,6 +298,8 @@ class KModel:
             raise NotImplementedError("Perturbed-Attention Guidance with a ControlNet / T2I-Adapter chain: the chain has no third group of rows")
         if self.diffusion_model._hooks(transformer_options) is not None:
             raise NotImplementedError("Perturbed-Attention Guidance (native) together with Python block hooks in transformer_options")
+        if lllite_of(transformer_options) is not None:
+            raise NotImplementedError(f"{LLLITE_FEATURE} with native Perturbed-Attention Guidance on the same job")
         sig_host = host_sigmas(sigma)
         shrink = shrink_for_step(transformer_options, sig_host)
         if shrink is not None:
@@ -351,15 +368,19 @@ class KModel:
             share = share_for_call(transformer_options, group_size_of_call(transformer_options, x.shape[0]))
             if share is not None and self.diffusion_model._hooks(transformer_options) is not None:
                 raise NotImplementedError("StyleAlign (native) together with Python block hooks in transformer_options")
+        lllite = lllite_for_call(transformer_options, self.diffusion_model._hooks(transformer_options),
+                                 (("StyleAlign", (transformer_options or {}).get(STYLEALIGN)), ("Kohya HRFix", (transformer_options or {}).get("kohya_hrfix"))))
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
         sigma = t.to(device=self.device, dtype=torch.float32).contiguous()
         ctxc = self.diffusion_model.prepare_context(c_crossattn, y)
         b, c, hh, ww = x.shape
         sig_host = host_sigmas(t)
         key = (b, c, hh, ww, 1, "apply") if share is None else (b, c, hh, ww, 1, "apply") + share_graph_key(share)
+        if lllite is not None:
+            key = key + lllite_graph_key(lllite)
         eps = self._forward_static(key, x, sigma, sig_host, 1, ctxc, control, transformer_options, c_concat,
                                    freeu=(transformer_options or {}).get("freeu_v2"), shrink=shrink_for_step(transformer_options, sig_host),
-                                   share=share)
+                                   share=share, lllite=lllite)
         return ops.cfg_combine(eps, eps.shape[-1], x, sigma, 1, 1.0, prediction_type=self.predictor.prediction_type,
                                sigma_data=self.predictor.sigma_data)
 
@@ -387,6 +408,8 @@ class KModelFlux:
             raise NotImplementedError("Kohya HRFix: UNet models only")
         if (transformer_options or {}).get("stylealign") is not None:
             raise NotImplementedError("StyleAlign: UNet models only")
+        if lllite_of(transformer_options) is not None:
+            raise NotImplementedError(f"{LLLITE_FEATURE}: UNet models only")
         if c_concat is not None or control is not None:
             raise NotImplementedError("c_concat / control are outside the txt2img hot path")
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
@@ -405,6 +428,8 @@ class KModelFlux:
             raise NotImplementedError("Kohya HRFix: UNet models only")
         if to.get("stylealign") is not None:
             raise NotImplementedError("StyleAlign: UNet models only")
+        if lllite_of(to) is not None:
+            raise NotImplementedError(f"{LLLITE_FEATURE}: UNet models only")
         if control_model is not None or to.get("patches") or to.get("patches_replace") or to.get("block_modifiers"):
             raise NotImplementedError("ControlNet / per-block hooks are built for the LDM UNet executor, not for the Flux transformer")
         ctx, y, guidance = cond_ctx

@@ -419,13 +419,24 @@ class IntegratedUNet2DConditionModel:
             padbuf = self._pad_bufs[key] = torch.zeros(*shape, dtype=torch.float16, device=self.device)
         return padbuf
 
-    def _attn_block(self, b, L, h, bu, n, ctxc, arena, rs1=None, want_next=False, pag_from=None, share=None):
+    def _lllite_operands(self, lllite, slots, x, n):
+        """[xq, xk, xv] of one attention under native ControlNet-LLLite: per projection that has a module x + module(x) * strength out of ONE launch
+        (ops.lllite_adapt, every module with its own cond embedding), and x itself -- no copy -- for a projection without one"""
+        if not any(s is not None for s in slots):
+            return [x, x, x]
+        outs = ops.lllite_adapt(x, None, n, [None if s is None else dict(s, cond=lllite.cond_emb(s)) for s in slots], lllite.strength)
+        return [x if o is None else o for o in outs]
+
+    def _attn_block(self, b, L, h, bu, n, ctxc, arena, rs1=None, want_next=False, pag_from=None, share=None, lllite=None):
         """One BasicTransformerBlock on h [M, C] (updated in place).  rs1: the row statistics the projection that WROTE h left (proj_in or the
         previous block's ff.net.2) -- norm1 then runs folded into the q|k and V^T projections; want_next: leave the statistics of this block's
         output for the next block's norm1.  pag_from: see _self_attention (everything but the attention itself runs on all rows).
         share: None, or native StyleAlign (backend/patcher/stylealign.py Share): the self-attention of every group of share.b images runs over
         their joined tokens ("aligned"), or is blended with the ordinary one ("blend", ops.attn_blend); see _shared_attention.  What governs the
         projections is then the token count of a group, T = b * n: tile-aligned T runs them dense (and folded) even where n alone is ragged.
+        lllite: None, or the native ControlNet-LLLite unit of this call (backend/patcher/lllite.py) when THIS block has modules: the norm in front
+        of an attention that has modules runs unfolded (its statistics rs1 / rs2 are not consumed), one ops.lllite_adapt makes the operands of
+        to_q / to_k / to_v, and the three projections read them separately; norm3 and the next block's norm1 fold as ever.
         -> that RowStats (or None)."""
         H, d = L.heads, L.dim_head
         dp = _dpad(d)
@@ -442,9 +453,21 @@ class IntegratedUNet2DConditionModel:
         own = share is None or share.mode == "blend"   # the ordinary per-image attention is wanted (into o)
         aligned = share is not None and share.mode == "aligned"
         o = sh = None
-        folded1 = seq % 64 == 0 and rs1 is not None and bool(rs1.parts) and (b + ".attn1.v.ln") in self.w
+        ll1 = lllite.blocks[b]["attn1"] if lllite is not None and any(s is not None for s in lllite.blocks[b]["attn1"]) else None
+        ll2 = lllite.blocks[b]["attn2"] if lllite is not None and any(s is not None for s in lllite.blocks[b]["attn2"]) else None
+        folded1 = seq % 64 == 0 and rs1 is not None and bool(rs1.parts) and (b + ".attn1.v.ln") in self.w and ll1 is None
         if seq % 64 == 0:
-            if folded1:
+            if ll1 is not None:
+                # (n % 64 == 0, no share: _forward_impl refused everything else)  q, k and v no longer share an input: three projections, the
+                # q and k ones into the two halves of the [Q | K] buffer the attention reads
+                n1 = ops.layernorm(h, *self.w[b + ".norm1"])
+                xq, xk, xv = self._lllite_operands(lllite, ll1, n1, n)
+                wqk = self.w[b + ".attn1.qk"]
+                qk = ops.empty((m_tok, 2 * hd))
+                ops.linear(xq, wqk[:hd], out=qk[:, :hd], ld_out=2 * hd)
+                ops.linear(xk, wqk[hd:], out=qk[:, hd:], ld_out=2 * hd)
+                vt = ops.conv_gemm(self.w[b + ".attn1.v"], xv, m_tok)          # [H*dp, M] = V^T (operand swap)
+            elif folded1:
                 wqk, csqk, bqk = self.w[b + ".attn1.qk.ln"]
                 ab = ops.empty((m_tok, 2), torch.float32)     # {rstd, -mean rstd} per token: the q|k GEMM derives them anyway and leaves them for V^T
                 qk = ops.conv_gemm(h, wqk, wqk.shape[0], bias=bqk, ln=(rs1, csqk, 1e-5), ln_ab_out=ab)   # [M, 2*H*dp] = [Q | K] of LN(h)
@@ -499,18 +522,21 @@ class IntegratedUNet2DConditionModel:
         ops.linear(o, *self.w[b + ".attn1.out"], residual=h, out=h, ld_out=h.shape[1], row_stats=rs2)
         arena.release(mk)
         self._tap(b + ".attn1", h.view(bu, n, -1))
-        self.fold_trace[b] = (folded1, bool(fold and rs2.parts), False)
+        self.fold_trace[b] = (folded1, bool(fold and rs2.parts) and ll2 is None, False)
         # cross attention against the cached text K / V^T
         kc, vtc = ctxc.kv[b]
         tp = ctxc.tpad
         # (round 5, off by default -- see _XATTN_FUSE) the whole of attn2 in ONE launch: a 256 x 320 tile of the query projection holds five whole 64-wide heads
         # of 256 queries of one image, so the attention against the cached K / V^T runs in that GEMM's epilogue out of the accumulators (fmx.h xa_*)
-        fused2 = (_XATTN_FUSE and fold and bool(rs2.parts) and self.tap is None and d == 64 and hd % 320 == 0 and n % 256 == 0 and ctxc.tokens <= 80 and tp >= 80)
+        fused2 = (ll2 is None and _XATTN_FUSE and fold and bool(rs2.parts) and self.tap is None and d == 64 and hd % 320 == 0 and n % 256 == 0 and ctxc.tokens <= 80 and tp >= 80)
         if fused2:
             wq, csq, bq = self.w[b + ".attn2.q.ln"]
             o2 = ops.conv_gemm(h, wq, wq.shape[0], bias=bq, ln=(rs2, csq, 1e-5), xattn=(kc, vtc, ctxc.tokens, tp, n, d ** -0.5))
         else:
-            if fold and rs2.parts:
+            if ll2 is not None:
+                n2 = ops.layernorm(h, *self.w[b + ".norm2"])
+                q2 = ops.linear(self._lllite_operands(lllite, ll2, n2, n)[0], self.w[b + ".attn2.q"])     # K / V^T: the cached text projections
+            elif fold and rs2.parts:
                 wq, csq, bq = self.w[b + ".attn2.q.ln"]
                 q2 = ops.conv_gemm(h, wq, wq.shape[0], bias=bq, ln=(rs2, csq, 1e-5))
             else:
@@ -634,7 +660,7 @@ class IntegratedUNet2DConditionModel:
             return h
         return r.permute(0, 2, 3, 1).to(torch.float16).contiguous()
 
-    def _spatial_transformer(self, L, x, ctxc, arena, to=None, pag_from=None, share=None):
+    def _spatial_transformer(self, L, x, ctxc, arena, to=None, pag_from=None, share=None, lllite=None):
         k = L.key
         bu, hh, ww, c = x.shape
         n = hh * ww
@@ -649,7 +675,11 @@ class IntegratedUNet2DConditionModel:
         # norm1 of every block folded into its q|k / V^T projections: the GEMM that writes h (proj_in, then each block's ff.net.2) leaves the row sums
         # (under native StyleAlign the attention sequence is a group's b * n tokens: that count decides, as in _attn_block)
         fold1 = _LN_FOLD and _LN_FOLD1 and not hooked and (n if share is None else share.b * n) % 64 == 0 and (f"{k}.transformer_blocks.0.attn1.v.ln") in self.w
-        rs1 = ops.RowStats(bu * n, inner) if fold1 else None
+        # native ControlNet-LLLite: a block with attn1 modules runs norm1 unfolded, so the GEMM in front of it need not leave the row sums
+        def ll_attn1(di):
+            e = lllite.blocks.get(f"{k}.transformer_blocks.{di}") if lllite is not None else None
+            return e is not None and any(s is not None for s in e["attn1"])
+        rs1 = ops.RowStats(bu * n, inner) if fold1 and not ll_attn1(0) else None
         h = ops.linear(g.view(-1, c), *self.w[k + ".proj_in"], row_stats=rs1)  # 1x1 conv == Linear in NHWC
         self._tap(k + ".proj_in", h.view(bu, n, -1))
         for di in range(L.depth):
@@ -657,8 +687,9 @@ class IntegratedUNet2DConditionModel:
                 to["block_index"] = di
                 self._attn_block_hooked(f"{k}.transformer_blocks.{di}", L, h, bu, n, ctxc, arena, to)
             else:
-                rs1 = self._attn_block(f"{k}.transformer_blocks.{di}", L, h, bu, n, ctxc, arena, rs1=rs1, want_next=fold1 and di + 1 < L.depth,
-                                       pag_from=pag_from, share=share)
+                bk = f"{k}.transformer_blocks.{di}"
+                rs1 = self._attn_block(bk, L, h, bu, n, ctxc, arena, rs1=rs1, want_next=fold1 and di + 1 < L.depth and not ll_attn1(di + 1),
+                                       pag_from=pag_from, share=share, lllite=lllite if lllite is not None and bk in lllite.blocks else None)
             self._tap(f"{k}.transformer_blocks.{di}", h.view(bu, n, -1))
         _, st = ops.linear(h, *self.w[k + ".proj_out"], residual=x.view(-1, c), out=out.view(-1, c), ld_out=c, n=bu, h=hh, w=ww, stats=True,
                            stats_partial=out_part)
@@ -687,7 +718,7 @@ class IntegratedUNet2DConditionModel:
             return Upsample(key=L.key)
         return Conv2d(key=L.key)
 
-    def _run_block(self, blk, h, skip, emb_all, ctxc, arena, up_to=None, to=None, pag_from=None, share=None):
+    def _run_block(self, blk, h, skip, emb_all, ctxc, arena, up_to=None, to=None, pag_from=None, share=None, lllite=None):
         inner = to.get("block_inner_modifiers", []) if to is not None else []
         wrapper = to.get("group_norm_wrapper") if to is not None else None
         standins = TimestepEmbedSequential(self._layer_standin(L) for L in blk) if inner else None
@@ -709,7 +740,7 @@ class IntegratedUNet2DConditionModel:
                 h = self._res(L, h, skip, emb_all, arena)
                 skip = None
             elif isinstance(L, SpatialT):
-                h = self._spatial_transformer(L, h, ctxc, arena, to, pag_from, share)
+                h = self._spatial_transformer(L, h, ctxc, arena, to, pag_from, share, lllite)
                 if to is not None and "transformer_index" in to:
                     to["transformer_index"] += 1  # unet.py:82-84
             elif isinstance(L, Down):
@@ -782,8 +813,38 @@ class IntegratedUNet2DConditionModel:
         self._concat_cache = (key, term, c_concat)
         return term
 
+    def _lllite_check(self, lllite, bu, hh, ww):
+        """Native ControlNet-LLLite, before any launch: every block the unit has modules for exists, has a multiple of 64 tokens per image and as
+        many as the modules' cond embeddings have rows.  The token counts follow from the layout: a Down halves (rounding up), an output block
+        runs at the size of the skip it pops."""
+        sizes, tokens = [], {}
+        for blk in self.layout.input_blocks:
+            for L in blk:
+                if isinstance(L, Down):
+                    hh, ww = (hh + 2 - 3) // 2 + 1, (ww + 2 - 3) // 2 + 1
+                elif isinstance(L, SpatialT):
+                    tokens[L.key] = hh * ww
+            sizes.append((hh, ww))
+        for L in self.layout.middle:
+            if isinstance(L, SpatialT):
+                tokens[L.key] = hh * ww
+        for blk in self.layout.output_blocks:
+            hh, ww = sizes.pop()
+            for L in blk:
+                if isinstance(L, SpatialT):
+                    tokens[L.key] = hh * ww
+        from ..patcher.lllite import FEATURE
+        for b in lllite.blocks:
+            n = tokens.get(b.rsplit(".transformer_blocks.", 1)[0])
+            if n is None or (b + ".norm1") not in self.w:
+                raise NotImplementedError(f"{FEATURE}: the file has modules for {b}, which this UNet does not have")
+            if n % 64 != 0:
+                raise NotImplementedError(f"{FEATURE} (native): {b} has {n} tokens per image, no multiple of 64; patch_lllite routes such a job to "
+                                          "its Python patches")
+            lllite.check_rows(b, n, bu)
+
     def _forward_impl(self, xcol, t, ctxc, bu, hh, ww, arena, control=None, to=None, concat_term=None, freeu=None, shrink=None, pag_from=None,
-                      share=None):
+                      share=None, lllite=None):
         """xcol: [Bu*H*W, 64] im2col of the (scaled) input; t: [Bu] fp32 table indices.  -> eps [Bu*H*W, out_ch].
         `to`: transformer_options with Python hooks (unet.py:696-763 hook points), or None on the fast path.
         `freeu`: a FreeUParams tuple (b1, b2, s1, s2, ...) of backend/patcher/freeu.py, or None: native FreeU v2 on the inputs of the
@@ -802,7 +863,16 @@ class IntegratedUNet2DConditionModel:
         `share`: None, or native StyleAlign (backend/patcher/stylealign.py Share(b, mode, strength); KModel hands it over for groups of b > 1 images):
         in EVERY transformer block of every level the self-attention of each group of b consecutive images runs over the group's joined tokens
         (the reference's set_model_replace_all(attn1_proc, "attn1")); attn2 is untouched.  With `pag_from` the perturbed group keeps V in the middle
-        block (the degraded pass replaces ("middle", 0) itself) and is one more group everywhere else.  Fast path, captured graph."""
+        block (the degraded pass replaces ("middle", 0) itself) and is one more group everywhere else.  Fast path, captured graph.
+        `lllite`: None, or the native ControlNet-LLLite unit (backend/patcher/lllite.py LLLite) of a call inside its window: the transformer blocks
+        it has modules for adapt the inputs of their q / k / v projections (_attn_block).  Fast path, captured graph."""
+        if lllite is not None:     # refused before any launch
+            from ..patcher.lllite import FEATURE as LLLITE
+            if to is not None:
+                raise NotImplementedError(f"{LLLITE} (native) together with Python block hooks in transformer_options")
+            if share is not None or pag_from is not None or shrink is not None:
+                raise NotImplementedError(f"{LLLITE} with native Perturbed-Attention Guidance, StyleAlign or Kohya HRFix on the same job")
+            self._lllite_check(lllite, bu, hh, ww)
         if share is not None:
             if share.b < 2 or bu % share.b != 0 or (pag_from is not None and pag_from % share.b != 0):
                 raise ValueError(f"StyleAlign groups of {share.b} images do not tile the batch of {bu} (perturbed group from {pag_from})")
@@ -878,7 +948,7 @@ class IntegratedUNet2DConditionModel:
                     h = self._call_nchw(m, h, "after", conv_in[0], 0, conv_in, to)
             else:
                 h = modify(h, "before")
-                h = self._run_block(blk, h, None, emb_all, ctxc, arena, to=to, share=share)
+                h = self._run_block(blk, h, None, emb_all, ctxc, arena, to=to, share=share, lllite=lllite)
             h = self._apply_control(h, control, "input")
             h = modify(h, "after")
             if shrink is not None and bi == shrink.block_number and not shrink.downscale_after_skip:
@@ -893,7 +963,7 @@ class IntegratedUNet2DConditionModel:
         if to is not None:
             to["block"] = ("middle", 0)
         h = modify(h, "before")
-        h = self._run_block(lay.middle, h, None, emb_all, ctxc, arena, to=to, pag_from=pag_from, share=share)
+        h = self._run_block(lay.middle, h, None, emb_all, ctxc, arena, to=to, pag_from=pag_from, share=share, lllite=lllite)
         h = self._apply_control(h, control, "middle")
         h = modify(h, "after")
         for bi, blk in enumerate(lay.output_blocks):
@@ -923,7 +993,7 @@ class IntegratedUNet2DConditionModel:
                 # halves separate (dual-input GroupNorm / conv), so it is materialised only when a modifier wants to see it
                 cat = modify(torch.cat([h, skip], dim=-1), "before")
                 h, skip = cat[..., :h.shape[-1]].contiguous(), cat[..., h.shape[-1]:].contiguous()
-            h = self._run_block(blk, h, skip, emb_all, ctxc, arena, up_to, to=to, share=share)
+            h = self._run_block(blk, h, skip, emb_all, ctxc, arena, up_to, to=to, share=share, lllite=lllite)
             h = modify(h, "after")
         if to is not None:
             to["block"] = ("last", 0)
@@ -968,17 +1038,17 @@ class IntegratedUNet2DConditionModel:
         return self._arena
 
     def forward_packed(self, xcol, t, ctxc, bu, hh, ww, control=None, transformer_options=None, concat_term=None, freeu=None, shrink=None,
-                       pag_from=None, share=None):
+                       pag_from=None, share=None, lllite=None):
         """Hot-path entry (no layout conversion): returns eps as fp16 [Bu*H*W, out_channels] living in the arena
         (valid until the next forward).  `freeu`, `shrink`: see _forward_impl (the caller takes them out of transformer_options["freeu_v2"] /
-        ["kohya_hrfix"]); `pag_from`, `share`: see _forward_impl."""
+        ["kohya_hrfix"]); `pag_from`, `share`, `lllite`: see _forward_impl."""
         while True:
             arena = self._get_arena(bu, hh, ww)
             arena.reset()
             try:
                 with arena:
                     return self._forward_impl(xcol, t, ctxc, bu, hh, ww, arena, control, self._hooks(transformer_options), concat_term, freeu,
-                                              shrink, pag_from, share)
+                                              shrink, pag_from, share, lllite)
             except ArenaOverflow:
                 torch.cuda.synchronize(self.device)
                 self._arena_bytes = arena.capacity * 2

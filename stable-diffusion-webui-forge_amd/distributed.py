@@ -36,6 +36,8 @@ def check_batch_coupled_options(model_options, world_size):
     raised by the sharded entry on every rank before any collective."""
     from .backend.patcher.stylealign import check_world
     check_world((model_options or {}).get("transformer_options"), world_size)
+    from .backend.patcher.lllite import check_world as lllite_check_world
+    lllite_check_world((model_options or {}).get("transformer_options"), world_size)    # image i of a call uses control image i % Bc
 
 
 def _flatten(cond):

@@ -869,6 +869,49 @@ def attn_blend(own, shared, strength, out=None):
     return out
 
 
+LLLITE_D, LLLITE_E = 64, 32     # the hidden width and the cond embedding width fmxl_lllite_adapt_f16 is built for
+
+
+def lllite_adapt(x, cond, rows_per_image, slots, multiplier):
+    """ControlNet-LLLite adapters on the input rows of one attention's q / k / v projections (include/fmx_lllite.h), one launch:
+    x [M, C] fp16 dense; slots: three entries for q, k, v, each None (no adapter) or a dict {wd [64, C], bd [64], wm [64, 96], bm [64], wu [C, 64],
+    bu [C]} of contiguous fp16 tensors, optionally with "cond" [Bc, rows_per_image, 32] (the module's own cond embedding; else `cond`, one embedding
+    for all slots) and "out" [M, C] (else allocated).  Image i of x uses embedding i % Bc.
+    -> [xq, xk, xv]: x + up(relu(mid(cat(cond, relu(down(x)))))) * multiplier per present slot, None for an absent one."""
+    assert len(slots) == 3
+    _check_f16(x, cond)
+    m, c = x.shape
+    assert x.is_contiguous()
+    structs, outs, dims = [], [], set()
+    for s in slots:
+        if s is None:
+            structs.append(None)
+            outs.append(None)
+            continue
+        ts = [s.get("cond", cond)] + [s[n] for n in ("wd", "bd", "wm", "bm", "wu", "bu")]
+        _check_f16(*ts)
+        ce, wd, bd, wm, bm, wu, bu = ts
+        assert ce is not None and all(t.is_contiguous() for t in ts)
+        assert ce.dim() == 3 and ce.shape[1] == rows_per_image
+        assert wd.shape[1] == c and wu.shape[0] == c and bu.shape[0] == c and wm.shape[0] == bm.shape[0] == bd.shape[0] == wu.shape[1] == wd.shape[0]
+        assert wm.shape[1] == ce.shape[2] + wd.shape[0]
+        out = s.get("out")
+        if out is None:
+            out = empty((m, c), torch.float16, x.device)
+        _check_f16(out)
+        assert out.shape == x.shape and out.is_contiguous()
+        structs.append(_lib.LlliteSlot(*(t.data_ptr() for t in ts), out.data_ptr()))
+        outs.append(out)
+        dims.add((wd.shape[0], ce.shape[2], ce.shape[0]))
+    assert len(dims) <= 1, "the slots of one launch share the hidden width, the embedding width and the number of cond images"
+    d, e, bc = dims.pop() if dims else (LLLITE_D, LLLITE_E, 1)
+    ptrs = [C.byref(s) if s is not None else None for s in structs]
+    ns = sum(o is not None for o in outs)
+    _timed("lllite", 2.0 * m * ns * (c * d + (e + d) * d + d * c),
+           lambda: _call("fmxl_lllite_adapt_f16", _p(x), m, c, d, e, rows_per_image, bc, *ptrs, float(multiplier)), nbytes=2.0 * m * c * (1 + ns))
+    return outs
+
+
 def euler_step(x, denoised, sigma, sigma_next, noise=None, noise_scale=0.0, out=None):
     if out is None:
         out = torch.empty_like(x)

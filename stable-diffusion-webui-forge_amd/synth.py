@@ -178,6 +178,67 @@ def synth_unet_state_dict(cfg, seed=0, **kw):
     return synth_state_dict(unet_param_shapes(cfg), seed=seed, **kw)
 
 
+# the tiny SDXL-shaped UNet with transformers on TWO levels (SDXL has them at 1/2 and 1/4 of the latent): what ControlNet-LLLite needs to meet both
+# of its conditioning depths (2 and 3).  The context is wider than the blocks' 128 channels: the reference's LLLite patch tells a self-attention
+# from a cross-attention by comparing the widths of q's and k's inputs
+TINY_SDXL_2LEVEL_UNET_CONFIG = dict(TINY_SDXL_UNET_CONFIG, num_res_blocks=[1, 1, 1], channel_mult=(1, 2, 2), transformer_depth=[0, 1, 1],
+                                    transformer_depth_middle=1, transformer_depth_output=[0, 0, 1, 1, 1, 1], context_dim=192)
+
+LLLITE_PROJECTIONS = ("attn1_to_q", "attn1_to_k", "attn1_to_v", "attn2_to_q")     # what the published SDXL files adapt
+
+
+def lllite_param_shapes(cfg, projections=LLLITE_PROJECTIONS, hidden=64, embed=32):
+    """name -> shape of a ControlNet-LLLite file (Linear modules) for every transformer block of the UNet `cfg`: a module per block and projection,
+    its conditioning chain as deep as the block's level asks (a level at 1 / 2^i of the latent is 1 / 2^(i+3) of the control image: depth i + 1)"""
+    from .backend.nn.layout import Down, SpatialT, unet_layout
+    lay = unet_layout(cfg)
+    levels, level, stack = {}, 0, []
+    for blk in lay.input_blocks:
+        for L in blk:
+            if isinstance(L, Down):
+                level += 1
+            elif isinstance(L, SpatialT):
+                levels[L.key] = (level, L)
+        stack.append(level)
+    for L in lay.middle:
+        if isinstance(L, SpatialT):
+            levels[L.key] = (level, L)
+    for blk in lay.output_blocks:
+        level = stack.pop()
+        for L in blk:
+            if isinstance(L, SpatialT):
+                levels[L.key] = (level, L)
+    shapes = OrderedDict()
+    for key, (level, L) in levels.items():
+        depth = level + 1
+        if not 1 <= depth <= 3:
+            raise ValueError(f"no LLLite conditioning depth for a transformer at level {level}")
+        c = L.heads * L.dim_head
+        half = embed // 2
+        convs = {1: [(half, 3, 4), (embed, half, 2)], 2: [(half, 3, 4), (embed, half, 4)], 3: [(half, 3, 4), (half, half, 4), (embed, half, 2)]}[depth]
+        for di in range(L.depth):
+            for proj in projections:
+                m = f"lllite_unet_{key.replace('.', '_')}_transformer_blocks_{di}_{proj}"
+                for i, (co, ci, k) in enumerate(convs):
+                    shapes[f"{m}.conditioning1.{2 * i}.weight"] = (co, ci, k, k)
+                    shapes[f"{m}.conditioning1.{2 * i}.bias"] = (co,)
+                for name, (o, i_) in (("down", (hidden, c)), ("mid", (hidden, embed + hidden)), ("up", (c, hidden))):
+                    shapes[f"{m}.{name}.0.weight"] = (o, i_)
+                    shapes[f"{m}.{name}.0.bias"] = (o,)
+    return shapes
+
+
+def synth_lllite_state_dict(cfg, seed=21, gain=1.0, up_gain=1.0, **kw):
+    """seeded ControlNet-LLLite weights for the UNet `cfg`.  Training starts `up` at zero; here it is drawn like every other layer, times `up_gain`,
+    so that a route that drops the adapters computes something else"""
+    sd = synth_state_dict(lllite_param_shapes(cfg, **kw), seed=seed, gain=gain)
+    if up_gain != 1.0:
+        for k in sd:
+            if ".up.0." in k:
+                sd[k] = sd[k] * up_gain
+    return sd
+
+
 def synth_controlnet_state_dict(cfg, hint_channels=3, seed=6, zero_conv_gain=1.0, **kw):
     """cldm.ControlNet weights.  Real checkpoints start from ZERO 1x1 output convs; random ones (same init as every other conv) make the
     residuals non-trivial for parity tests."""

@@ -1,0 +1,364 @@
+"""CPU: native ControlNet-LLLite -- the key split, the conditioning depth and the call counter against the sequences the reference's own module
+recorded; every refusal and both fallbacks to the Python patches; the graph keys; include/fmx_lllite.h under the rules of the other two headers;
+python_patch against what the reference's patch object and modules recorded; the derived bound of the kernel test against an fp32 emulation of the
+kernel and against every planted bug."""
+import ctypes as C
+import glob
+import os
+import re
+import subprocess
+from types import SimpleNamespace
+
+import pytest
+import torch
+
+import forge_amd  # noqa: F401
+from forge_amd import _lib, synth
+from forge_amd import distributed as fdist
+from forge_amd.backend.modules import k_model
+from forge_amd.backend.nn.layout import unet_layout
+from forge_amd.backend.nn.unet import IntegratedUNet2DConditionModel as UNetExecutor
+from forge_amd.backend.patcher import lllite as ll
+from forge_amd.backend.patcher.kohya_hrfix import patch_kohya_hrfix
+from forge_amd.backend.patcher.lllite import ControlLLLitePatcher, patch_lllite
+from forge_amd.backend.patcher.pag import patch_pag
+from forge_amd.backend.patcher.stylealign import patch_stylealign
+from forge_amd.backend.patcher.unet import UnetPatcher
+
+from conftest import load_golden
+import lllite_refs as L
+from test_pag_host import BADARG, FAKE, _kmodel, _patcher, _Reached
+
+CFG = dict(synth.TINY_SDXL_2LEVEL_UNET_CONFIG)
+
+
+@pytest.fixture(scope="module")
+def fx():
+    return load_golden("lllite.pt")
+
+
+@pytest.fixture(scope="module")
+def lsd(fx):
+    return synth.synth_lllite_state_dict(CFG, seed=fx["lllite_seed"], gain=fx["lllite_gain"], up_gain=fx["up_gain"])
+
+
+def images(fx, size=None):
+    return L.control_images(fx["bc"], size or (fx["hw"][0] * 8, fx["hw"][1] * 8), fx["image_seed"])
+
+
+def unit(fx, lsd, patcher=None, size=None, **kw):
+    return patch_lllite(patcher or _patcher(), lsd, images(fx, size), **kw)
+
+
+# ---- key split, depth, step arithmetic ------------------------------------------------------------------------------------------------------------------
+def test_key_split_targets_and_depths(fx, lsd):
+    mods = ll.split_modules(lsd)
+    assert len(mods) == 28 and all(set(w) >= {"down.0.weight", "mid.0.bias", "up.0.weight", "conditioning1.0.weight"} for w in mods.values())
+    assert ll.module_target("lllite_unet_input_blocks_4_1_transformer_blocks_1_attn1_to_k") == ("input_blocks.4.1.transformer_blocks.1", "attn1", "k")
+    assert ll.module_target("lllite_unet_middle_block_1_transformer_blocks_9_attn2_to_q") == ("middle_block.1.transformer_blocks.9", "attn2", "q")
+    assert ll.module_target("lllite_unet_output_blocks_3_1_transformer_blocks_0_attn1_to_v") == ("output_blocks.3.1.transformer_blocks.0", "attn1", "v")
+    with pytest.raises(ValueError, match="names no transformer block projection"):
+        ll.module_target("lllite_unet_input_blocks_4_0_in_layers_2")
+    depth = {name: ll.module_depth(w) for name, w in mods.items()}
+    assert {d for n, d in depth.items() if "input_blocks_3" in n or "output_blocks_2" in n or "output_blocks_3" in n} == {2}
+    assert {d for n, d in depth.items() if "input_blocks_5" in n or "middle_block" in n or "output_blocks_0" in n or "output_blocks_1" in n} == {3}
+    one = {"conditioning1.0.weight": torch.zeros(16, 3, 4, 4), "conditioning1.2.weight": torch.zeros(32, 16, 2, 2)}
+    assert ll.module_depth(one) == 1
+    lll = unit(fx, lsd).model_options["transformer_options"]["lllite"]
+    assert sorted(lll.blocks) == sorted(f"{k}.transformer_blocks.0" for k in ("input_blocks.3.1", "input_blocks.5.1", "middle_block.1", "output_blocks.0.1",
+                                                                            "output_blocks.1.1", "output_blocks.2.1", "output_blocks.3.1"))
+    for entry in lll.blocks.values():
+        assert all(s is not None for s in entry["attn1"]) and entry["attn2"][0] is not None and entry["attn2"][1:] == [None, None]
+    rows = {lll.emb_rows(s) for s in lll.blocks["input_blocks.3.1.transformer_blocks.0"]["attn1"]}
+    assert rows == {256} and lll.emb_rows(lll.blocks["middle_block.1.transformer_blocks.0"]["attn2"][0]) == 64
+    assert ll.block_name_of_options({"block": ("output", 2), "block_index": 0}) == "output_blocks.2.1.transformer_blocks.0"
+
+
+def test_call_counter_is_the_references_recorded_sequence(fx):
+    assert [(c["steps"], c["start"], c["end"]) for c in fx["counter"]] == [(0, 0.0, 0.0), (10, 0.0, 0.0), (10, 0.25, 0.7), (7, 0.5, 0.0)]
+    for c in fx["counter"]:
+        n = len(c["active"])
+        assert n == (int(2.5 * c["steps"]) or 5)
+        counter = ll.CallCounter(c["steps"], c["start"], c["end"])
+        assert [counter.advance() for _ in range(n)] == c["active"] == L.counter_sequence(c["steps"], c["start"], c["end"], n), c
+    assert ll.step_window(10, 0.25, 0.7) == (2, 7) and ll.step_window(7, 0.5, 0.0) == (3, 7) and ll.step_window(0, 0.3, 0.6) == (0, 0)
+    # the window wraps: (10, 0.25, 0.7) is on again at call 12
+    assert fx["counter"][2]["active"][12] and not fx["counter"][2]["active"][10]
+
+
+# ---- refusals ---------------------------------------------------------------------------------------------------------------------------------------------
+def test_refusals_at_the_patcher(fx, lsd):
+    flux = k_model.KModelFlux.__new__(k_model.KModelFlux)
+    with pytest.raises(NotImplementedError, match="ControlNet-LLLite: UNet models only"):
+        patch_lllite(UnetPatcher(model=flux), lsd, images(fx))
+    name = "lllite_unet_middle_block_1_transformer_blocks_0_attn1_to_q"
+    conv = dict(lsd)
+    conv[name + ".down.0.weight"] = lsd[name + ".down.0.weight"][:, :, None, None]
+    with pytest.raises(NotImplementedError, match="Conv2d module"):
+        unit(fx, conv)
+    wide = dict(lsd)
+    wide[name + ".down.0.weight"] = torch.zeros(128, 128)
+    with pytest.raises(NotImplementedError, match="hidden width 128"):
+        unit(fx, wide)
+    emb = dict(lsd)
+    emb[name + ".conditioning1.0.weight"] = torch.zeros(32, 3, 4, 4)
+    with pytest.raises(NotImplementedError, match="cond embedding width 64"):
+        unit(fx, emb)
+    for proj in "kv":
+        bad = {k.replace("attn2_to_q", "attn2_to_" + proj): v for k, v in lsd.items()}
+        with pytest.raises(NotImplementedError, match=f"adapts the {proj} projection of a cross-attention"):
+            unit(fx, bad)
+    with pytest.raises(NotImplementedError, match="ControlNet-LLLite with native Perturbed-Attention Guidance"):
+        unit(fx, lsd, patch_pag(_patcher(), 3.0))
+    with pytest.raises(NotImplementedError, match="ControlNet-LLLite with native StyleAlign"):
+        unit(fx, lsd, patch_stylealign(_patcher(), 0.5))
+    with pytest.raises(NotImplementedError, match="ControlNet-LLLite with native Kohya HRFix"):
+        unit(fx, lsd, patch_kohya_hrfix(_patcher(), 3, 2.0, 0.0, 0.35, True, "bicubic", "bicubic"))
+    hooked = _patcher()
+    hooked.set_model_attn1_output_patch(lambda out, extra: out)
+    with pytest.raises(NotImplementedError, match="ControlNet-LLLite together with Python block hooks"):
+        unit(fx, lsd, hooked)
+
+
+def test_refusals_at_the_model_call_come_before_any_launch(fx, lsd, monkeypatch):
+    net, km, packs = _kmodel(monkeypatch)
+    net.prepare_context = lambda *a: pytest.fail("refusals come before the context is prepared")
+    to = unit(fx, lsd).model_options["transformer_options"]
+    x = torch.zeros(2, 4, 32, 32)
+    c, uc = (torch.ones(2, 77, 8), None), (torch.zeros(2, 77, 8), None)
+    sig = torch.ones(2, dtype=torch.float64)
+    sig.fmx_sigma = k_model.SigmaInfo([1.0, 1.0])
+    with pytest.raises(NotImplementedError, match="ControlNet-LLLite.*Python block hooks"):
+        km.denoise_cfg(x, sig, uc, c, 7.0, transformer_options=dict(to, patches={"attn1_output_patch": [lambda o, e: o]}))
+    with pytest.raises(NotImplementedError, match="ControlNet-LLLite with native StyleAlign"):
+        km.denoise_cfg(x, sig, uc, c, 7.0, transformer_options=dict(to, **patch_stylealign(_patcher(), 0.5).model_options["transformer_options"]))
+    kohya = patch_kohya_hrfix(_patcher(), 3, 2.0, 0.0, 0.35, True, "bicubic", "bicubic").model_options["transformer_options"]
+    with pytest.raises(NotImplementedError, match="ControlNet-LLLite with native Kohya HRFix"):
+        km.denoise_cfg(x, sig, uc, c, 7.0, transformer_options=dict(to, **kohya))
+    with pytest.raises(NotImplementedError, match="ControlNet-LLLite with native Perturbed-Attention Guidance"):
+        km.denoise_cfg(x, sig, uc, c, 7.0, transformer_options=to, pag_scale=3.0)
+    with pytest.raises(NotImplementedError, match="ControlNet-LLLite.*Python block hooks"):
+        km.apply_model(x, sig, c_crossattn=c[0], transformer_options=dict(to, patches={"attn1_output_patch": [lambda o, e: o]}))
+    lll = to["lllite"]
+    with pytest.raises(NotImplementedError, match="ControlNet-LLLite.*Python block hooks"):
+        km._forward_static((2, 4, 32, 32, 2), x, None, [1.0, 1.0], 2, None, transformer_options={"patches": {"attn1_patch": [len]}}, lllite=lll)
+    with pytest.raises(NotImplementedError, match="ControlNet-LLLite.*Python block hooks"):
+        UNetExecutor._forward_impl(None, None, None, None, 4, 32, 32, None, to={"patches": {}}, lllite=lll)
+    with pytest.raises(NotImplementedError, match="ControlNet-LLLite with native"):
+        UNetExecutor._forward_impl(None, None, None, None, 4, 32, 32, None, pag_from=2, lllite=lll)
+    assert packs == [] and net.calls == [] and lll.counter.current == 0
+    flux = k_model.KModelFlux.__new__(k_model.KModelFlux)
+    with pytest.raises(NotImplementedError, match="ControlNet-LLLite: UNet models only"):
+        flux.apply_model(torch.zeros(2, 16, 8, 8), sig, transformer_options=to)
+    with pytest.raises(NotImplementedError, match="ControlNet-LLLite: UNet models only"):
+        flux.denoise_cfg(torch.zeros(2, 16, 8, 8), sig, None, (None, None, None), 1.0, transformer_options=to)
+
+
+def test_embedding_rows_and_unknown_blocks_are_refused_by_the_executors_walk(fx, lsd):
+    net = SimpleNamespace(layout=unet_layout(CFG), w={f"{k}.transformer_blocks.0.norm1": 1 for k in
+                                                     ("input_blocks.3.1", "input_blocks.5.1", "middle_block.1", "output_blocks.0.1", "output_blocks.1.1",
+                                                      "output_blocks.2.1", "output_blocks.3.1")})
+    lll = unit(fx, lsd).model_options["transformer_options"]["lllite"]
+    UNetExecutor._lllite_check(net, lll, 4, 32, 32)                  # the fixture's job: 256 and 64 tokens, a batch of 2 x Bc
+    with pytest.raises(NotImplementedError, match="cond embedding of 256 rows, the block has 1024 tokens"):
+        UNetExecutor._lllite_check(net, lll, 4, 64, 64)              # a latent the control image does not fit
+    with pytest.raises(NotImplementedError, match="batch of 3 images is no multiple of the 2 control images"):
+        UNetExecutor._lllite_check(net, lll, 3, 32, 32)
+    sdxl_named = {k.replace("input_blocks_3_1", "input_blocks_4_1"): v for k, v in lsd.items()}
+    with pytest.raises(NotImplementedError, match="modules for input_blocks.4.1.transformer_blocks.0, which this UNet does not have"):
+        UNetExecutor._lllite_check(net, unit(fx, sdxl_named).model_options["transformer_options"]["lllite"], 4, 32, 32)
+
+
+def test_a_sharded_batch_is_refused(fx, lsd):
+    mo = unit(fx, lsd).model_options
+    with pytest.raises(NotImplementedError, match="ControlNet-LLLite.*2 ranks"):
+        fdist.check_batch_coupled_options(mo, 2)
+    fdist.check_batch_coupled_options(mo, 1)
+    fdist.check_batch_coupled_options(_patcher().model_options, 8)
+    python_route = unit(fx, lsd, size=(128, 128)).model_options        # embeddings of 64 and 16 rows: the Python patches
+    with pytest.raises(NotImplementedError, match="ControlNet-LLLite.*4 ranks"):
+        fdist.check_batch_coupled_options(python_route, 4)
+
+
+# ---- the two fallbacks ------------------------------------------------------------------------------------------------------------------------------------
+def test_ragged_embeddings_and_a_second_unit_take_the_python_patches(fx, lsd):
+    native = unit(fx, lsd)
+    to = native.model_options["transformer_options"]
+    assert isinstance(to["lllite"], ll.LLLite) and "patches" not in to and UNetExecutor._hooks(to) is None
+    assert to["lllite"].native_ok()
+    ragged = unit(fx, lsd, size=(128, 128)).model_options["transformer_options"]       # 8 x 8 and 4 x 4 tokens
+    assert "lllite" not in ragged and UNetExecutor._hooks(ragged) is not None
+    assert len(ragged["patches"]["attn1_patch"]) == 1 and ragged["patches"]["attn1_patch"][0] is ragged["patches"]["attn2_patch"][0]
+    assert isinstance(ragged["patches"]["attn1_patch"][0], ll.PythonPatch)
+    second = unit(fx, lsd, native, strength=0.5).model_options["transformer_options"]
+    assert "lllite" not in second and [p.lll.strength for p in second["patches"]["attn1_patch"]] == [1.0, 0.5]
+    assert second["patches"]["attn1_patch"][0].lll is to["lllite"] and "patches" not in to        # the first patcher is untouched
+    third = unit(fx, lsd, unit(fx, lsd, unit(fx, lsd, native)))
+    assert len(third.model_options["transformer_options"]["patches"]["attn2_patch"]) == 4
+    # the control-unit entry: selection by key, the unit's weight and window
+    assert ControlLLLitePatcher.try_build_from_state_dict({"input_blocks.0.0.weight": torch.zeros(1)}) is None
+    cu = ControlLLLitePatcher.try_build_from_state_dict(lsd)
+    cu.strength, cu.start_percent, cu.end_percent = 0.7, 0.25, 0.7
+    objs = SimpleNamespace(unet=_patcher())
+    process = SimpleNamespace(steps=10, sd_model=SimpleNamespace(forge_objects=objs))
+    cu.process_before_every_sampling(process, images(fx).movedim(-1, 1), None)
+    got = objs.unet.model_options["transformer_options"]["lllite"]
+    assert (got.strength, got.counter.steps, got.counter.start, got.counter.end) == (0.7, 10, 2, 7)
+    from forge_amd.backend.patcher import controlnet as pc
+    assert isinstance(pc.load_controlnet(lsd), ControlLLLitePatcher)
+
+
+# ---- graph keys -------------------------------------------------------------------------------------------------------------------------------------------
+def test_graph_keys_plain_outside_the_window_unit_and_strength_inside(fx, lsd, monkeypatch):
+    net, km, packs = _kmodel(monkeypatch)
+    seen = []
+    net.forward_packed = lambda *a, **kw: (seen.append(kw.get("lllite")), (_ for _ in ()).throw(_Reached()))[1]
+    monkeypatch.setattr(ll.LLLite, "prepare", lambda self: None)
+    x = torch.zeros(2, 4, 32, 32)
+    c, uc = (torch.ones(2, 77, 8), None), (torch.zeros(2, 77, 8), None)
+    sig = torch.ones(2, dtype=torch.float64)
+    sig.fmx_sigma = k_model.SigmaInfo([1.0, 1.0])
+    to = unit(fx, lsd, strength=0.8, steps=4, start_percent=0.25, end_percent=0.75).model_options["transformer_options"]
+    lll = to["lllite"]
+    for _ in range(5):                      # calls 0 .. 4 of a window [1, 3) that wraps at 4: off, on, on, off, off
+        with pytest.raises(_Reached):
+            km.denoise_cfg(x, sig, uc, c, 7.0, transformer_options=to)
+    assert seen == [None, lll, lll, None, None]
+    base = (2, 4, 32, 32, 2)
+    assert list(km._static) == [base, base + ("lllite", lll.serial, 0.8)] and list(km._gstate) == list(km._static)
+    # another unit, or the same file at another strength: its own key
+    other = unit(fx, lsd, strength=0.5).model_options["transformer_options"]
+    with pytest.raises(_Reached):
+        km.denoise_cfg(x, sig, uc, c, 7.0, transformer_options=other)
+    assert list(km._static)[-1] == base + ("lllite", other["lllite"].serial, 0.5) and other["lllite"].serial != lll.serial
+    with pytest.raises(_Reached):
+        km.apply_model(torch.zeros(4, 4, 32, 32), sig, c_crossattn=torch.zeros(4, 77, 8), transformer_options=other)
+    assert list(km._static)[-1] == (4, 4, 32, 32, 1, "apply", "lllite", other["lllite"].serial, 0.5) and seen[-1] is other["lllite"]
+    # a native option, not a Python hook
+    assert UNetExecutor._hooks(to) is None
+
+
+# ---- include/fmx_lllite.h ---------------------------------------------------------------------------------------------------------------------------------
+def test_the_entry_point_is_named_in_a_gpu_test():
+    here = os.path.dirname(os.path.abspath(__file__))
+    gpu_tests = "".join(open(f).read() for f in glob.glob(os.path.join(here, "test_gpu_*.py")))
+    assert _lib.LLLITE_SIGNATURES and all(re.search(r"\b" + name + r"\b", gpu_tests) for name in _lib.LLLITE_SIGNATURES), sorted(_lib.LLLITE_SIGNATURES)
+
+
+def test_library_exports_the_symbol_and_checks_its_contract():
+    lib = _lib.lib()
+    f = lib.fmxl_lllite_adapt_f16
+    i64, i32, f32, vp, sp = C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.POINTER(_lib.LlliteSlot)
+    assert _lib.LLLITE_SIGNATURES == {"fmxl_lllite_adapt_f16": [vp, i64, i32, i32, i32, i32, i32, sp, sp, sp, f32, vp]}
+    assert not set(_lib.LLLITE_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES))
+    assert _lib.CONSTANTS["FMX_ABI_VERSION"] == 12 and lib.fmx_abi_version() == 12
+    assert [n for n, _ in _lib.LlliteSlot._fields_] == ["cond", "wd", "bd", "wm", "bm", "wu", "bu", "out"]
+    text = re.sub(r"/\*.*?\*/", "", open(_lib.LLLITE_HEADER).read(), flags=re.S)
+    declared = set(re.findall(r"\b(fmxl_[a-z0-9_]+)\s*\(", text))
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {ln.split()[-1] for ln in out.splitlines() if re.search(r" T fmxl_", ln)}
+    assert declared == exported == set(_lib.LLLITE_SIGNATURES)
+    assert f.argtypes == _lib.LLLITE_SIGNATURES["fmxl_lllite_adapt_f16"]
+    err = lambda: lib.fmx_last_error().decode()  # noqa: E731
+    m, c = 256, 320
+
+    def slot(i=0, **kw):
+        # distinct 16-byte aligned fake addresses, 1 MiB apart: validation never dereferences them
+        p = {n: FAKE + (8 * i + j) * (1 << 20) for j, n in enumerate(["cond", "wd", "bd", "wm", "bm", "wu", "bu", "out"])}
+        p.update(kw)
+        return _lib.LlliteSlot(*(p[n] for n, _ in _lib.LlliteSlot._fields_))
+
+    def call(x=FAKE + (1 << 30), m=m, c=c, d=64, e=32, n=64, bc=1, q=None, k=None, v=None):
+        ref = lambda s: None if s is None else C.byref(s)  # noqa: E731
+        return f(vp(x), m, c, d, e, n, bc, ref(q), ref(k), ref(v), 1.0, None)
+    q = slot(0)
+    for kw, text_ in ((dict(d=32), "hidden width 32"), (dict(e=64), "cond embedding width 64"), (dict(c=328), "c = 328"), (dict(c=1344), "c = 1344"),
+                      (dict(c=0), "c = 0"), (dict(m=0), "m = 0"), (dict(m=96), "m = 96"), (dict(n=96), "rows_per_image = 96"), (dict(n=0), "rows_per_image = 0"),
+                      (dict(n=192), "rows_per_image = 192"), (dict(bc=0), "cond_images = 0"), (dict(x=0), "null"), (dict(x=FAKE + 8), "16-byte aligned")):
+        assert call(q=q, **kw) == BADARG and text_ in err(), (kw, err())
+    assert call() == BADARG and "no slot" in err()
+    for name in ("cond", "wd", "bd", "wm", "bm", "wu", "bu", "out"):
+        assert call(k=slot(1, **{name: 0})) == BADARG and "null pointer in slot 1" in err()
+        assert call(v=slot(2, **{name: FAKE + 2})) == BADARG and "slot 2 must be 16-byte aligned" in err()
+    assert call(q=slot(0, out=FAKE + (1 << 30))) == BADARG and "slot 0 aliases x" in err()
+    assert call(q=slot(0, out=FAKE + (1 << 30) + m * c * 2 - 16)) == BADARG and "aliases x" in err()       # the last 16 bytes of x
+    assert call(q=q, v=slot(2, out=FAKE + 7 * (1 << 20) + 4096)) == BADARG and "slot 2 aliases another out" in err()
+
+
+# ---- python_patch against the reference -------------------------------------------------------------------------------------------------------------------
+def test_cond_embeddings_are_the_references(fx, lsd):
+    lll = unit(fx, lsd).model_options["transformer_options"]["lllite"]
+    assert set(fx["cond_emb"]) == set(lll.modules)
+    worst = 0.0
+    for name, want in fx["cond_emb"].items():
+        got = lll.cond_emb_torch(lll.modules[name], torch.float32)
+        assert got.shape == want.shape == (fx["bc"], lll.emb_rows(lll.modules[name]), 32) and want.dtype == torch.float16
+        # the fixture stores the reference's fp32 embedding rounded to fp16: half an fp16 ulp per value, plus fp32 noise
+        err = float(((got.double() - want.double()).abs() / (0.5 * L.ulp16(got.double()) + 1e-6)).max())
+        worst = max(worst, err)
+        assert err <= 1.0, (name, err)
+    print("cond embeddings through torch vs the reference's (stored as fp16): worst", worst, "x half an ulp")
+
+
+def test_python_patch_equals_the_references_recorded_calls(fx, lsd):
+    """the reference's patch object was called on the middle block with seeded inputs (tools/make_lllite_fixtures.py patch_calls); python_patch on
+    the same inputs, in fp32 on the CPU: the same torch ops, to fp32 rounding.  Measured: 3e-7 max-normalised; the gate is 1e-5."""
+    assert [(c["kind"], c["strength"]) for c in fx["patch_calls"]] == [("attn1", 1.0), ("attn2", 0.5)]
+    for c in fx["patch_calls"]:
+        g = torch.Generator().manual_seed(c["seed"])
+        q, ctx = torch.randn(2, 64, 128, generator=g), torch.randn(2, 77, 192, generator=g)
+        kv = q if c["kind"] == "attn1" else ctx
+        patch = unit(fx, lsd, strength=c["strength"]).model_options["transformer_options"]["lllite"].python_patch()
+        out = patch(q, kv, kv, {"block": c["block"], "block_index": c["block_index"]})
+        for got, want, src in zip(out, c["out"], (q, kv, kv)):
+            got = got[:, ::c["every"]]
+            assert got.shape == want.shape and got.dtype == torch.float32
+            err = float((got - want).abs().max() / want.abs().max())
+            assert err <= 1e-5, (c["kind"], err)
+        assert (c["kind"] == "attn2") == (out[1] is kv) and not torch.equal(out[0], q)
+    # a block without modules, and a call outside the window, hand the inputs back
+    assert patch(q, q, q, {"block": ("input", 1), "block_index": 0}) == (q, q, q)
+    off = unit(fx, lsd, steps=4, start_percent=0.5).model_options["transformer_options"]["lllite"].python_patch()
+    assert off(q, q, q, {"block": ("middle", 0), "block_index": 0})[0] is q
+    # the fixture moved: a route that drops the adapters cannot pass a gate keyed to the floor
+    for tag, floor in fx["floor"].items():
+        assert min(fx["moved"][tag], fx["swapped"][tag]) >= 10 * floor["rms_rel"], tag
+
+
+# ---- the kernel test's bound --------------------------------------------------------------------------------------------------------------------------------
+def test_fp32_emulation_of_the_kernel_sits_within_the_bound_on_every_gpu_case():
+    worst = 0.0
+    for c in L.CHANNELS:
+        for images_, n, bc in L.GEOMETRIES:
+            x, conds, slots = L.make_case(c, images_, n, bc)
+            for mult in L.MULTIPLIERS:
+                for s in range(3):
+                    y, bound = L.adapt_ref(x, conds[s], n, slots[s], mult)
+                    got = L.adapt_emul32(x, conds[s], n, slots[s], mult)
+                    e = L.excess(got, y, bound)
+                    worst = max(worst, e)
+                    assert e <= 1.0, (c, images_, n, bc, mult, s, e)
+                    if mult == 0.0:
+                        assert torch.equal(got, x)
+    print("fp32 emulation of fmxl_lllite_adapt_f16, worst ratio to the bound:", worst)
+    assert worst > 0.05      # the bound is not vacuous either
+
+
+def test_every_planted_bug_exceeds_the_bound_four_times():
+    x, conds, slots = L.make_case(320, 4, 64, 2)
+    measured = {}
+    for bug in L.BUGS:
+        per_slot = []
+        for s in range(3):
+            y, bound = L.adapt_ref(x, conds[s], 64, slots[s], 0.35)
+            if bug == "k_uses_q_weights":
+                if s != 1:
+                    continue
+                got = L.adapt_emul32(x, conds[1], 64, slots[0], 0.35)
+            else:
+                got = L.adapt_emul32(x, conds[s], 64, slots[s], 0.35, bug=bug)
+            per_slot.append(L.excess(got, y, bound))
+        measured[bug] = min(per_slot)
+        assert measured[bug] >= L.TEETH_FACTOR, (bug, per_slot)
+    print("planted bugs, excess over the bound:", {k: round(v, 1) for k, v in measured.items()})
+    assert set(measured) == set(L.MEASURED_EXCESS) and all(abs(measured[k] / v - 1.0) < 0.05 for k, v in L.MEASURED_EXCESS.items()), measured

@@ -14,6 +14,8 @@ batch sizes -- and what they cost.
                                                      interleaved in one process, device events around every job
     python tools/bench_features.py --only stylealign StyleAlign: plain / native at strength 1.0 and 0.5 (captured graph) / the reference's attn1 replace
                                                     patch at both strengths on the hooked executor, timed alternately in one process
+    python tools/bench_features.py --only lllite     ControlNet-LLLite: plain / native (fused adapter kernel, captured graph) / the same unit as Python
+                                                     attn1 / attn2 patches on the hooked executor, and the adapter launches on their own
     python tools/bench_features.py --only taesd      the TAESD decode of batch x (res/8)^2 SDXL-shaped latents (synthetic weights, fp16) next to the Full
                                                      VAE decode of the same latents in the same process: median of 5 after warm-up, events around the calls
 """
@@ -459,6 +461,101 @@ def main():
                           "own_attention_plus_blend_ms_per_step": round(med["stylealign_native_0.5"] - med["stylealign_native_1.0"], 2),
                           "finite": finite, "shape": list(lat.shape)}), flush=True)
 
+    def lllite_leg(rounds=3):
+        """Plain, native ControlNet-LLLite (transformer option "lllite": fmxl_lllite_adapt_f16 in front of the q / k / v projections of every
+        transformer block, captured graph) and the same unit as Python attn1 / attn2 patches on the eager hooked executor (backend/patcher/lllite.py
+        python_patch) -- seeded weights for every transformer block of the network (attn1 q / k / v and attn2 q: what the published SDXL files
+        adapt), one control image, always on.  Primed once each, then timed alternately, `rounds` jobs of a.steps steps per route in this one
+        process, device events around each job.  Also the adapter launches of one UNet call on their own (device events, median of 20 per distinct
+        shape) with their algorithmic bytes: what the kernel itself costs, next to what the unfolded norms and the split projections cost."""
+        import lllite_refs as lr
+        from forge_amd import hipops as ops
+        from forge_amd.backend.patcher.lllite import patch_lllite
+        base = eng.forge_objects.unet
+        lsd = synth.synth_lllite_state_dict(cfg, seed=21, gain=2.0, up_gain=0.5)
+        image = lr.control_images(1, (height, width), 5)
+        native = patch_lllite(base, lsd, image, 1.0)
+        lll = native.model_options["transformer_options"]["lllite"]
+        python = base.clone()
+        patch = lll.python_patch()
+        python.set_model_attn1_patch(patch)
+        python.set_model_attn2_patch(patch)
+        variants = {"plain": None, "lllite_native": native, "lllite_python": python}
+        saved = eng.forge_objects_after_applying_lora
+        shapes = []                       # (m, c, slots) of every ops.lllite_adapt call
+        real = ops.lllite_adapt
+        ops.lllite_adapt = lambda x, cond, n, slots, mult: (shapes.append((x.shape[0], x.shape[1], n, sum(s is not None for s in slots))),
+                                                            real(x, cond, n, slots, mult))[1]
+
+        def once(unet, n):
+            if unet is not None:
+                eng.forge_objects_after_applying_lora = saved.shallow_copy()
+                eng.forge_objects_after_applying_lora.unet = unet
+            try:
+                pr = processing.StableDiffusionProcessingTxt2Img(sd_model=eng, c=c1, uc=u1, seed=1, sampler_name="Euler", batch_size=b, steps=n,
+                                                                 cfg_scale=7.0, width=width, height=height, do_decode=False)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                lat = processing.process_images(pr).latents
+                e1.record()
+                torch.cuda.synchronize()
+                return e0.elapsed_time(e1), lat
+            finally:
+                eng.forge_objects_after_applying_lora = saved
+                eng.forge_objects = saved.shallow_copy()
+        try:
+            for k, unet in variants.items():    # priming (arena, caches, graphs)
+                n_before = len(shapes)
+                once(unet, 4)
+                if k == "lllite_native":
+                    calls = len(shapes) - n_before
+        finally:
+            ops.lllite_adapt = real
+        launches = len(lll.blocks) * 2          # per UNet call: attn1 and attn2 of every block that has modules
+        per_call = shapes[:launches]
+        ms = {k: [] for k in variants}
+        finite = True
+        for _ in range(rounds):
+            for k, unet in variants.items():
+                once(unet, 2)             # a job on another route came before: what follows a change of route is not timed
+                dt, lat = once(unet, a.steps)
+                ms[k].append(round(dt / a.steps, 2))
+                finite = finite and bool(torch.isfinite(lat).all())
+        med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+        # the adapter launches of one UNet call on their own
+        kernel_ms, kernel_bytes, by_shape = 0.0, 0.0, {}
+        for shape in sorted(set(per_call)):
+            m_, c_, n_, ns = shape
+            x = torch.randn(m_, c_, device=dev).half()
+            slots = [dict({k: v.to(dev) for k, v in lr.make_slot(c_, i).items()}, cond=(torch.randn(1, n_, 32, device=dev) * 0.7).half(),
+                          out=torch.empty(m_, c_, dtype=torch.float16, device=dev)) if i < ns else None for i in range(3)]
+            times = []
+            for _ in range(23):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                real(x, None, n_, slots, 1.0)
+                e1.record()
+                torch.cuda.synchronize()
+                times.append(e0.elapsed_time(e1))
+            t = sorted(times[3:])[10]
+            count = per_call.count(shape)
+            nbytes = 2.0 * m_ * c_ * (1 + ns)
+            by_shape[f"M={m_} C={c_} slots={ns}"] = {"launches_per_unet_call": count, "ms": round(t, 4), "GBps_read_plus_write": round(nbytes / t / 1e6, 1)}
+            kernel_ms += count * t
+            kernel_bytes += count * nbytes
+        print(json.dumps({"case": f"ControlNet-LLLite ({len(lll.modules)} modules on {len(lll.blocks)} transformer blocks, batch {b}): plain vs native "
+                                  "(captured graph) vs the Python route (attn1 / attn2 patches, eager hooked executor)", "sampler": "Euler", "steps": a.steps,
+                          "rounds": rounds, "ms_per_step": med, "ms_per_step_rounds": ms, "native_over_plain": round(med["lllite_native"] / med["plain"], 3),
+                          "python_over_native": round(med["lllite_python"] / med["lllite_native"], 3),
+                          "adapter_launches_per_unet_call": len(per_call), "adapter_launches_seen_while_priming": calls,
+                          "adapter_kernel_ms_per_unet_call": round(kernel_ms, 3), "adapter_kernel_bytes_per_unet_call": kernel_bytes,
+                          "adapter_kernel_GBps_read_plus_write": round(kernel_bytes / kernel_ms / 1e6, 1),
+                          "adapter_kernels_share_of_native_step": round(kernel_ms / med["lllite_native"], 4), "adapter_kernel_by_shape": by_shape,
+                          "finite": finite, "shape": list(lat.shape)}), flush=True)
+
+    if "lllite" in what:
+        lllite_leg()
     if "one" in what:
         run(f"{width}x{height}", sampler="Euler")
     if "stylealign" in what:
