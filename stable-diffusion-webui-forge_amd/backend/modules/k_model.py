@@ -10,6 +10,7 @@ import torch
 from ... import hipops as ops
 from ...runtime import HipGraph
 from ..patcher.kohya_hrfix import shrink_for_step, shrink_graph_key
+from ..patcher.ipadapter import FEATURE as IPADAPTER_FEATURE, ipadapter_for_call, units_of as ipadapter_units_of
 from ..patcher.lllite import FEATURE as LLLITE_FEATURE, lllite_for_call, lllite_graph_key, lllite_of
 from ..patcher.stylealign import OPTION as STYLEALIGN, group_size_of_call, share_for_call, share_graph_key
 
@@ -90,7 +91,7 @@ class KModel:
         return entries
 
     def _forward_static(self, key, x, sigma_dev, sig_host, reps, ctxc, control=None, transformer_options=None, c_concat=None, control_plan=None,
-                        freeu=None, shrink=None, pag_from=None, share=None, lllite=None):
+                        freeu=None, shrink=None, pag_from=None, share=None, lllite=None, ipadapter=None):
         """pack -> [ControlNets ->] UNet -> (returns eps view); static buffers per shape so the chain can be graph-replayed.
         `reps`: the stacked copies of the batch: 1, 2 ([uncond ; cond]) or, with the perturbed group of native Perturbed-Attention Guidance
         behind them, 2 or 3; `pag_from`: the first image of that group (backend/nn/unet.py), or None.  Such a call arrives with ("pag",) in `key`,
@@ -106,7 +107,16 @@ class KModel:
         arguments, so its static buffers and its graph are its own.
         `lllite`: the job's native ControlNet-LLLite unit (transformer_options["lllite"], backend/patcher/lllite.py) when this MODEL CALL lies inside
         its window -- the caller advanced the unit's call counter -- else None.  Such a call arrives with ("lllite", unit, strength) in `key`: the
-        blocks that have modules launch other kernels; a call outside the window is the plain call on the plain graph."""
+        blocks that have modules launch other kernels; a call outside the window is the plain call on the plain graph.
+        `ipadapter`: the prepared ExtraContext of native IP-Adapter (transformer_options["ipadapter"], backend/patcher/ipadapter.py) when this
+        step's host sigma lies inside the window of at least one unit, else None.  Such a call arrives with the context's graph key in `key` --
+        the active set of units, each unit's identity, weight and weight type, the group order: the cached image K / V^T are captured addresses,
+        the weights launch arguments -- so the steps inside and outside a window are two graphs; outside, the call is the plain call."""
+        if ipadapter is not None:     # refused before any launch
+            if self.diffusion_model._hooks(transformer_options) is not None:
+                raise NotImplementedError(f"{IPADAPTER_FEATURE} (native) together with Python block hooks in transformer_options")
+            if pag_from is not None or lllite is not None:
+                raise NotImplementedError(f"{IPADAPTER_FEATURE} with native Perturbed-Attention Guidance or ControlNet-LLLite on the same job")
         if share is not None and self.diffusion_model._hooks(transformer_options) is not None:     # refused before any launch
             raise NotImplementedError("StyleAlign (native) together with Python block hooks in transformer_options")
         if lllite is not None:     # refused before any launch
@@ -152,7 +162,7 @@ class KModel:
         if not self.use_graph or control is not None or hooks is not None:
             # Python hooks cannot be captured, and a ControlNet chain that needs Python per step arrives here with its residuals: eager
             return net.forward_packed(st["xcol"], st["t"], ctxc, bu, hh, ww, control, hooks, concat_term, freeu=freeu, shrink=shrink,
-                                      pag_from=pag_from, share=share, lllite=lllite)
+                                      pag_from=pag_from, share=share, lllite=lllite, ipadapter=ipadapter)
         active = [e for e in control_plan if e["active"]] if control_plan else []
         gkey = key if not active else key + ("control",) + tuple(e["cm"].exec_serial for e in active)
         if freeu is not None:
@@ -169,7 +179,7 @@ class KModel:
                 outs = e["cm"].forward_static(st["xcol"], st["t"], e["ctxc"], bu, hh, ww, e["gh"])
                 ctrl = e["cn"].control_merge(None, outs, ctrl, torch.float32)
             return net.forward_packed(st["xcol"], st["t"], ctxc, bu, hh, ww, control=ctrl, concat_term=concat_term, freeu=freeu, shrink=shrink,
-                                      pag_from=pag_from, share=share, lllite=lllite)
+                                      pag_from=pag_from, share=share, lllite=lllite, ipadapter=ipadapter)
 
         def validity():
             # What a captured graph points at: the executors' arenas (re-allocated when a larger shape comes through, e.g. the hires pass),
@@ -262,6 +272,9 @@ class KModel:
         per_call_options = transformer_options
         sig_host = host_sigmas(sigma)
         shrink = shrink_for_step(job_options, sig_host)    # native as well; the window is tested on the host's copy of sigma
+        # native IP-Adapter: the units whose window holds this step's host sigma, their image K / V^T prepared (outside any capture)
+        ipadapter = ipadapter_for_call(job_options, sig_host[0], [1, 0] if reps == 2 else [0], reps * b, self.diffusion_model,
+                                       self.diffusion_model._hooks(job_options), (("ControlNet-LLLite", lllite_of(job_options)),))
         if reps == 2:
             ctx = self._stack_ctx(uncond_ctx, cond_ctx)
         else:
@@ -270,6 +283,8 @@ class KModel:
         key = (b, c, hh, ww, reps) if share is None else (b, c, hh, ww, reps) + share_graph_key(share)
         if lllite is not None:
             key = key + lllite_graph_key(lllite)
+        if ipadapter is not None:
+            key = key + ipadapter.graph_key()
         control, plan = None, None
         if control_model is not None:
             # sampling_function.py:261-268: every ControlNet of the chain sees the per-call options, then one get_control on the stacked batch
@@ -285,7 +300,7 @@ class KModel:
                 t_all.fmx_sigma = SigmaInfo(list(sig_host) * reps)
                 control = control_model.get_control(torch.cat([x] * reps), t_all, {"c_crossattn": ctx[0], "y": ctx[1]}, reps)
         eps = self._forward_static(key, x, sigma, sig_host, reps, ctxc, control=control, transformer_options=transformer_options, c_concat=c_concat,
-                                   control_plan=plan, freeu=freeu, shrink=shrink, share=share, lllite=lllite)
+                                   control_plan=plan, freeu=freeu, shrink=shrink, share=share, lllite=lllite, ipadapter=ipadapter)
         cond_pred = torch.empty_like(x) if want_parts else None
         uncond_pred = torch.empty_like(x) if want_parts else None
         den = ops.cfg_combine(eps, eps.shape[-1], x, sigma, reps, cond_scale, None, cond_pred, uncond_pred,
@@ -300,6 +315,8 @@ class KModel:
             raise NotImplementedError("Perturbed-Attention Guidance (native) together with Python block hooks in transformer_options")
         if lllite_of(transformer_options) is not None:
             raise NotImplementedError(f"{LLLITE_FEATURE} with native Perturbed-Attention Guidance on the same job")
+        if ipadapter_units_of(transformer_options) is not None:
+            raise NotImplementedError(f"{IPADAPTER_FEATURE} with native Perturbed-Attention Guidance on the same job: its third row group has no image tokens")
         sig_host = host_sigmas(sigma)
         shrink = shrink_for_step(transformer_options, sig_host)
         if shrink is not None:
@@ -378,9 +395,14 @@ class KModel:
         key = (b, c, hh, ww, 1, "apply") if share is None else (b, c, hh, ww, 1, "apply") + share_graph_key(share)
         if lllite is not None:
             key = key + lllite_graph_key(lllite)
+        # native IP-Adapter: the groups are the entries of the caller's cond_or_uncond; refused before any launch when they are unknown or repeat
+        ipadapter = ipadapter_for_call(transformer_options, sig_host[0], (transformer_options or {}).get("cond_or_uncond"), b, self.diffusion_model,
+                                       self.diffusion_model._hooks(transformer_options), (("ControlNet-LLLite", lllite_of(transformer_options)),))
+        if ipadapter is not None:
+            key = key + ipadapter.graph_key()
         eps = self._forward_static(key, x, sigma, sig_host, 1, ctxc, control, transformer_options, c_concat,
                                    freeu=(transformer_options or {}).get("freeu_v2"), shrink=shrink_for_step(transformer_options, sig_host),
-                                   share=share, lllite=lllite)
+                                   share=share, lllite=lllite, ipadapter=ipadapter)
         return ops.cfg_combine(eps, eps.shape[-1], x, sigma, 1, 1.0, prediction_type=self.predictor.prediction_type,
                                sigma_data=self.predictor.sigma_data)
 
@@ -410,6 +432,8 @@ class KModelFlux:
             raise NotImplementedError("StyleAlign: UNet models only")
         if lllite_of(transformer_options) is not None:
             raise NotImplementedError(f"{LLLITE_FEATURE}: UNet models only")
+        if ipadapter_units_of(transformer_options) is not None:
+            raise NotImplementedError(f"{IPADAPTER_FEATURE}: UNet models only")
         if c_concat is not None or control is not None:
             raise NotImplementedError("c_concat / control are outside the txt2img hot path")
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
@@ -430,6 +454,8 @@ class KModelFlux:
             raise NotImplementedError("StyleAlign: UNet models only")
         if lllite_of(to) is not None:
             raise NotImplementedError(f"{LLLITE_FEATURE}: UNet models only")
+        if ipadapter_units_of(to) is not None:
+            raise NotImplementedError(f"{IPADAPTER_FEATURE}: UNet models only")
         if control_model is not None or to.get("patches") or to.get("patches_replace") or to.get("block_modifiers"):
             raise NotImplementedError("ControlNet / per-block hooks are built for the LDM UNet executor, not for the Flux transformer")
         ctx, y, guidance = cond_ctx

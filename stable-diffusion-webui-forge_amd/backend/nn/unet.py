@@ -407,6 +407,35 @@ class IntegratedUNet2DConditionModel:
                 ops.attn_value_rows(vt[:, g * tpad:], o[g * t_seq:], first=0, count=gb, n=n, hd=hd, vt_bs=n, vt_ds=cols)
         return o
 
+    def _cross_attention(self, b, q2, kc, vtc, bu, n, tokens, tp, H, d, ipadapter=None):
+        """O [Bu * n, H * dp] of attn2 against the cached text K / V^T.  ipadapter: None, or native IP-Adapter's ExtraContext
+        (backend/patcher/ipadapter.py): O = text attention + sum over the units of weight * attention over the unit's image tokens, the images of
+        group g (Bu // groups consecutive ones) reading group g's tokens.  Heads up to 64 wide (padded to 64) against at most 128 text keys: ONE launch of
+        ops.attention_dual, the units as segments of the cached extra context (one read of Q, one write of O).  Every other head width -- and
+        ipadapter.force_composite, the timing baseline -- the composite route on existing kernels: the text attention, one attention per unit and
+        group into arena scratch, ops.add_scaled_.  The adapter touches neither Q nor the norm in front of it."""
+        dp = _dpad(d)
+        hd = H * dp
+        kw = dict(heads=H, nq=n, dpad=dp, scale=d ** -0.5, q_bs=n * hd, q_rs=hd)
+        text = dict(batch=bu, nk=tokens, nk_pad=tp, k_bs=tp * hd, k_rs=hd, vt_bs=tp, vt_hs=dp * bu * tp, vt_ds=bu * tp)
+        if ipadapter is None:
+            return ops.attention(q2, kc, vtc, **kw, **text)
+        ent = ipadapter.blocks[b]
+        groups = len(ipadapter.cond_or_uncond)
+        ipg = bu // groups
+        if dp == 64 and tokens <= 128 and not ipadapter.force_composite:
+            return ops.attention_dual(q2, kc, vtc, ent["xk"], ent["xvt"], ent["segments"], images_per_group=ipg, **kw, **text)
+        o2 = ops.attention(q2, kc, vtc, **kw, **text)
+        xkeys = ent["xk"].shape[1]
+        for xk_u, xvt_u, count, weight in ent["units"]:
+            ou = ops.empty((bu * n, hd))
+            for g in range(groups):     # the images of a group share the unit's keys: batch strides of 0
+                rows = slice(g * ipg * n, (g + 1) * ipg * n)
+                ops.attention(q2[rows], xk_u[g], xvt_u[:, g * xkeys:], batch=ipg, nk=count, nk_pad=xkeys, k_bs=0, k_rs=hd, vt_bs=0, vt_hs=dp * groups * xkeys,
+                              vt_ds=groups * xkeys, out=ou[rows], **kw)
+            ops.add_scaled_(o2, ou, weight)
+        return o2
+
     def _pad_buf(self, key, shape):
         """persistent zero-filled LayerNorm output for ragged token counts (see _attn_block); bounded, and captured graphs that point at a dropped
         buffer are invalidated via the epoch"""
@@ -427,7 +456,7 @@ class IntegratedUNet2DConditionModel:
         outs = ops.lllite_adapt(x, None, n, [None if s is None else dict(s, cond=lllite.cond_emb(s)) for s in slots], lllite.strength)
         return [x if o is None else o for o in outs]
 
-    def _attn_block(self, b, L, h, bu, n, ctxc, arena, rs1=None, want_next=False, pag_from=None, share=None, lllite=None):
+    def _attn_block(self, b, L, h, bu, n, ctxc, arena, rs1=None, want_next=False, pag_from=None, share=None, lllite=None, ipadapter=None):
         """One BasicTransformerBlock on h [M, C] (updated in place).  rs1: the row statistics the projection that WROTE h left (proj_in or the
         previous block's ff.net.2) -- norm1 then runs folded into the q|k and V^T projections; want_next: leave the statistics of this block's
         output for the next block's norm1.  pag_from: see _self_attention (everything but the attention itself runs on all rows).
@@ -528,7 +557,7 @@ class IntegratedUNet2DConditionModel:
         tp = ctxc.tpad
         # (round 5, off by default -- see _XATTN_FUSE) the whole of attn2 in ONE launch: a 256 x 320 tile of the query projection holds five whole 64-wide heads
         # of 256 queries of one image, so the attention against the cached K / V^T runs in that GEMM's epilogue out of the accumulators (fmx.h xa_*)
-        fused2 = (ll2 is None and _XATTN_FUSE and fold and bool(rs2.parts) and self.tap is None and d == 64 and hd % 320 == 0 and n % 256 == 0 and ctxc.tokens <= 80 and tp >= 80)
+        fused2 = (ll2 is None and ipadapter is None and _XATTN_FUSE and fold and bool(rs2.parts) and self.tap is None and d == 64 and hd % 320 == 0 and n % 256 == 0 and ctxc.tokens <= 80 and tp >= 80)
         if fused2:
             wq, csq, bq = self.w[b + ".attn2.q.ln"]
             o2 = ops.conv_gemm(h, wq, wq.shape[0], bias=bq, ln=(rs2, csq, 1e-5), xattn=(kc, vtc, ctxc.tokens, tp, n, d ** -0.5))
@@ -543,8 +572,7 @@ class IntegratedUNet2DConditionModel:
                 n2 = ops.layernorm(h, *self.w[b + ".norm2"])
                 q2 = ops.linear(n2, self.w[b + ".attn2.q"])
             self._tap_qkv(b + ".attn2", q2.view(bu, n, hd), kc.view(bu, tp, hd)[:, :ctxc.tokens], vtc.view(hd, bu, tp)[:, :, :ctxc.tokens])
-            o2 = ops.attention(q2, kc, vtc, batch=bu, heads=H, nq=n, nk=ctxc.tokens, nk_pad=tp, dpad=dp, scale=d ** -0.5,
-                               q_bs=n * hd, q_rs=hd, k_bs=tp * hd, k_rs=hd, vt_bs=tp, vt_hs=dp * bu * tp, vt_ds=bu * tp)
+            o2 = self._cross_attention(b, q2, kc, vtc, bu, n, ctxc.tokens, tp, H, d, ipadapter)
         self._tap(b + ".attn2.o", o2.view(bu, n, -1))
         ops.linear(o2, *self.w[b + ".attn2.out"], residual=h, out=h, ld_out=h.shape[1], row_stats=rs3)
         arena.release(mk)
@@ -660,7 +688,7 @@ class IntegratedUNet2DConditionModel:
             return h
         return r.permute(0, 2, 3, 1).to(torch.float16).contiguous()
 
-    def _spatial_transformer(self, L, x, ctxc, arena, to=None, pag_from=None, share=None, lllite=None):
+    def _spatial_transformer(self, L, x, ctxc, arena, to=None, pag_from=None, share=None, lllite=None, ipadapter=None):
         k = L.key
         bu, hh, ww, c = x.shape
         n = hh * ww
@@ -689,7 +717,8 @@ class IntegratedUNet2DConditionModel:
             else:
                 bk = f"{k}.transformer_blocks.{di}"
                 rs1 = self._attn_block(bk, L, h, bu, n, ctxc, arena, rs1=rs1, want_next=fold1 and di + 1 < L.depth and not ll_attn1(di + 1),
-                                       pag_from=pag_from, share=share, lllite=lllite if lllite is not None and bk in lllite.blocks else None)
+                                       pag_from=pag_from, share=share, lllite=lllite if lllite is not None and bk in lllite.blocks else None,
+                                       ipadapter=ipadapter)
             self._tap(f"{k}.transformer_blocks.{di}", h.view(bu, n, -1))
         _, st = ops.linear(h, *self.w[k + ".proj_out"], residual=x.view(-1, c), out=out.view(-1, c), ld_out=c, n=bu, h=hh, w=ww, stats=True,
                            stats_partial=out_part)
@@ -718,7 +747,7 @@ class IntegratedUNet2DConditionModel:
             return Upsample(key=L.key)
         return Conv2d(key=L.key)
 
-    def _run_block(self, blk, h, skip, emb_all, ctxc, arena, up_to=None, to=None, pag_from=None, share=None, lllite=None):
+    def _run_block(self, blk, h, skip, emb_all, ctxc, arena, up_to=None, to=None, pag_from=None, share=None, lllite=None, ipadapter=None):
         inner = to.get("block_inner_modifiers", []) if to is not None else []
         wrapper = to.get("group_norm_wrapper") if to is not None else None
         standins = TimestepEmbedSequential(self._layer_standin(L) for L in blk) if inner else None
@@ -740,7 +769,7 @@ class IntegratedUNet2DConditionModel:
                 h = self._res(L, h, skip, emb_all, arena)
                 skip = None
             elif isinstance(L, SpatialT):
-                h = self._spatial_transformer(L, h, ctxc, arena, to, pag_from, share, lllite)
+                h = self._spatial_transformer(L, h, ctxc, arena, to, pag_from, share, lllite, ipadapter)
                 if to is not None and "transformer_index" in to:
                     to["transformer_index"] += 1  # unet.py:82-84
             elif isinstance(L, Down):
@@ -844,7 +873,7 @@ class IntegratedUNet2DConditionModel:
             lllite.check_rows(b, n, bu)
 
     def _forward_impl(self, xcol, t, ctxc, bu, hh, ww, arena, control=None, to=None, concat_term=None, freeu=None, shrink=None, pag_from=None,
-                      share=None, lllite=None):
+                      share=None, lllite=None, ipadapter=None):
         """xcol: [Bu*H*W, 64] im2col of the (scaled) input; t: [Bu] fp32 table indices.  -> eps [Bu*H*W, out_ch].
         `to`: transformer_options with Python hooks (unet.py:696-763 hook points), or None on the fast path.
         `freeu`: a FreeUParams tuple (b1, b2, s1, s2, ...) of backend/patcher/freeu.py, or None: native FreeU v2 on the inputs of the
@@ -865,7 +894,18 @@ class IntegratedUNet2DConditionModel:
         (the reference's set_model_replace_all(attn1_proc, "attn1")); attn2 is untouched.  With `pag_from` the perturbed group keeps V in the middle
         block (the degraded pass replaces ("middle", 0) itself) and is one more group everywhere else.  Fast path, captured graph.
         `lllite`: None, or the native ControlNet-LLLite unit (backend/patcher/lllite.py LLLite) of a call inside its window: the transformer blocks
-        it has modules for adapt the inputs of their q / k / v projections (_attn_block).  Fast path, captured graph."""
+        it has modules for adapt the inputs of their q / k / v projections (_attn_block).  Fast path, captured graph.
+        `ipadapter`: None, or the prepared ExtraContext of native IP-Adapter (backend/patcher/ipadapter.py) for a call inside a unit's window: every
+        cross-attention adds the units' image-token attention to the text attention (_cross_attention).  Fast path, captured graph."""
+        if ipadapter is not None:     # refused before any launch
+            from ..patcher.ipadapter import FEATURE as IPADAPTER, check_cond_or_uncond
+            if to is not None:
+                raise NotImplementedError(f"{IPADAPTER} (native) together with Python block hooks in transformer_options")
+            if pag_from is not None:
+                raise NotImplementedError(f"{IPADAPTER} with native Perturbed-Attention Guidance on the same job: its third row group has no image tokens")
+            if lllite is not None:
+                raise NotImplementedError(f"{IPADAPTER} with native ControlNet-LLLite on the same job")
+            check_cond_or_uncond(ipadapter.cond_or_uncond, bu)
         if lllite is not None:     # refused before any launch
             from ..patcher.lllite import FEATURE as LLLITE
             if to is not None:
@@ -948,7 +988,7 @@ class IntegratedUNet2DConditionModel:
                     h = self._call_nchw(m, h, "after", conv_in[0], 0, conv_in, to)
             else:
                 h = modify(h, "before")
-                h = self._run_block(blk, h, None, emb_all, ctxc, arena, to=to, share=share, lllite=lllite)
+                h = self._run_block(blk, h, None, emb_all, ctxc, arena, to=to, share=share, lllite=lllite, ipadapter=ipadapter)
             h = self._apply_control(h, control, "input")
             h = modify(h, "after")
             if shrink is not None and bi == shrink.block_number and not shrink.downscale_after_skip:
@@ -963,7 +1003,7 @@ class IntegratedUNet2DConditionModel:
         if to is not None:
             to["block"] = ("middle", 0)
         h = modify(h, "before")
-        h = self._run_block(lay.middle, h, None, emb_all, ctxc, arena, to=to, pag_from=pag_from, share=share, lllite=lllite)
+        h = self._run_block(lay.middle, h, None, emb_all, ctxc, arena, to=to, pag_from=pag_from, share=share, lllite=lllite, ipadapter=ipadapter)
         h = self._apply_control(h, control, "middle")
         h = modify(h, "after")
         for bi, blk in enumerate(lay.output_blocks):
@@ -993,7 +1033,7 @@ class IntegratedUNet2DConditionModel:
                 # halves separate (dual-input GroupNorm / conv), so it is materialised only when a modifier wants to see it
                 cat = modify(torch.cat([h, skip], dim=-1), "before")
                 h, skip = cat[..., :h.shape[-1]].contiguous(), cat[..., h.shape[-1]:].contiguous()
-            h = self._run_block(blk, h, skip, emb_all, ctxc, arena, up_to, to=to, share=share, lllite=lllite)
+            h = self._run_block(blk, h, skip, emb_all, ctxc, arena, up_to, to=to, share=share, lllite=lllite, ipadapter=ipadapter)
             h = modify(h, "after")
         if to is not None:
             to["block"] = ("last", 0)
@@ -1038,17 +1078,17 @@ class IntegratedUNet2DConditionModel:
         return self._arena
 
     def forward_packed(self, xcol, t, ctxc, bu, hh, ww, control=None, transformer_options=None, concat_term=None, freeu=None, shrink=None,
-                       pag_from=None, share=None, lllite=None):
+                       pag_from=None, share=None, lllite=None, ipadapter=None):
         """Hot-path entry (no layout conversion): returns eps as fp16 [Bu*H*W, out_channels] living in the arena
         (valid until the next forward).  `freeu`, `shrink`: see _forward_impl (the caller takes them out of transformer_options["freeu_v2"] /
-        ["kohya_hrfix"]); `pag_from`, `share`, `lllite`: see _forward_impl."""
+        ["kohya_hrfix"]); `pag_from`, `share`, `lllite`, `ipadapter`: see _forward_impl."""
         while True:
             arena = self._get_arena(bu, hh, ww)
             arena.reset()
             try:
                 with arena:
                     return self._forward_impl(xcol, t, ctxc, bu, hh, ww, arena, control, self._hooks(transformer_options), concat_term, freeu,
-                                              shrink, pag_from, share, lllite)
+                                              shrink, pag_from, share, lllite, ipadapter)
             except ArenaOverflow:
                 torch.cuda.synchronize(self.device)
                 self._arena_bytes = arena.capacity * 2

@@ -347,12 +347,18 @@ class ControlLora(ControlNet):
 
 def load_controlnet(controlnet_data, unet_config=None, device="cuda"):
     """State dict -> patcher-level control object.  ControlNet-LLLite files carry 'lllite' in their keys (-> a ControlLLLitePatcher, whose
-    process_before_every_sampling patches the job's UNet); Control-LoRA files carry the `lora_controlnet` marker and need no config (it is the UNet's);
+    process_before_every_sampling patches the job's UNet); IP-Adapter files carry `ip_adapter` keys (-> an IPAdapterPatcher, likewise);
+    Control-LoRA files carry the `lora_controlnet` marker and need no config (it is the UNet's);
     a full ControlNet (LDM keys) is built on `unet_config`, the configuration of the UNet family it was trained for."""
     if any("lllite" in k for k in controlnet_data.keys()):
         # ControlNet-LLLite: no second network and no residuals, a patch of the UNet's own transformer blocks (backend/patcher/lllite.py)
         from .lllite import ControlLLLitePatcher
         return ControlLLLitePatcher.try_build_from_state_dict(controlnet_data)
+    from ..nn.ipadapter import is_ipadapter_file
+    if is_ipadapter_file(controlnet_data):
+        # IP-Adapter: no second network and no residuals either, an extra context for the UNet's own cross-attentions (backend/patcher/ipadapter.py)
+        from .ipadapter import IPAdapterPatcher
+        return IPAdapterPatcher.try_build_from_state_dict(controlnet_data)
     if "lora_controlnet" in controlnet_data:
         return ControlLora(controlnet_data, device=device)
     if "zero_convs.0.0.weight" not in controlnet_data:

@@ -38,6 +38,8 @@ def check_batch_coupled_options(model_options, world_size):
     check_world((model_options or {}).get("transformer_options"), world_size)
     from .backend.patcher.lllite import check_world as lllite_check_world
     lllite_check_world((model_options or {}).get("transformer_options"), world_size)    # image i of a call uses control image i % Bc
+    from .backend.patcher.ipadapter import check_world as ipadapter_check_world
+    ipadapter_check_world((model_options or {}).get("transformer_options"), world_size)  # image b of a call reads the tokens of its group
 
 
 def _flatten(cond):

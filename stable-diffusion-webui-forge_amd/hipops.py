@@ -371,6 +371,48 @@ def attention(q, k, vt, *, batch, heads, nq, nk, nk_pad, dpad, scale, q_bs, q_rs
     return out
 
 
+DUAL_MAX_SEGMENTS, DUAL_EXTRA_KEYS = _lib.IPADAPTER_CONSTANTS["FMXI_MAX_SEGMENTS"], _lib.IPADAPTER_CONSTANTS["FMXI_EXTRA_KEYS"]
+
+
+def attention_dual(q, k, vt, xk, xvt, segments, *, batch, heads, nq, nk, nk_pad, dpad, scale, images_per_group, q_bs, q_rs, k_bs, k_rs, vt_bs, vt_hs,
+                   vt_ds, out=None, o_bs=None):
+    """Cross-attention over the text context plus the segments of an extra context in one launch (include/fmx_ipadapter.h):
+    O = attention(q, k, vt) + sum over (start, count, weight) in `segments` of weight * attention(q, xk[start : start + count], xv[...]).
+    q / k / vt / out / o_bs and the strides are those of attention().  xk: [groups, 64, heads * 64] contiguous, xvt: [heads * 64, groups * 64]
+    contiguous V^T, finite everywhere; image b reads group b // images_per_group.  1..4 disjoint segments inside [0, 64).  dpad == 64 and
+    nk <= 128 only: the library refuses everything else (the executor's composite route runs those on attention())."""
+    _check_f16(q, k, vt, xk, xvt, out)
+    if batch % images_per_group:
+        raise ValueError(f"attention_dual: batch {batch} is not a multiple of images_per_group {images_per_group}")
+    groups = batch // images_per_group
+    hd = heads * 64
+    if tuple(xk.shape) != (groups, DUAL_EXTRA_KEYS, hd) or tuple(xvt.shape) != (hd, groups * DUAL_EXTRA_KEYS) or not (xk.is_contiguous() and xvt.is_contiguous()):
+        raise ValueError(f"attention_dual: xk {tuple(xk.shape)} / xvt {tuple(xvt.shape)} are not the contiguous [{groups}, {DUAL_EXTRA_KEYS}, {hd}] / "
+                         f"[{hd}, {groups * DUAL_EXTRA_KEYS}] extra context")
+    segments = [(int(s), int(c), float(w)) for s, c, w in segments]
+    if not 1 <= len(segments) <= DUAL_MAX_SEGMENTS:
+        raise ValueError(f"attention_dual: {len(segments)} segments, not 1..{DUAL_MAX_SEGMENTS}")
+    if out is None:
+        out = empty((batch * nq, heads * dpad), torch.float16, q.device)
+    a = _lib.DualAttnArgs()
+    a.q, a.k, a.vt, a.o, a.xk, a.xvt = _p(q), _p(k), _p(vt), _p(out), _p(xk), _p(xvt)
+    a.q_bs, a.q_rs, a.k_bs, a.k_rs = q_bs, q_rs, k_bs, k_rs
+    a.vt_bs, a.vt_hs, a.vt_ds = vt_bs, vt_hs, vt_ds
+    a.o_bs, a.o_rs = (nq * out.stride(0) if o_bs is None else int(o_bs)), out.stride(0)
+    a.batch, a.heads, a.nq, a.nk, a.nk_pad, a.dpad = batch, heads, nq, nk, nk_pad, dpad
+    a.scale, a.images_per_group, a.nseg = float(scale), int(images_per_group), len(segments)
+    a.zero_page = _p(zero_page(q.device))
+    for i, (s, c, w) in enumerate(segments):
+        setattr(a, f"seg_start{i}", s)
+        setattr(a, f"seg_count{i}", c)
+        setattr(a, f"seg_weight{i}", w)
+    d_true = int(round(float(scale) ** -2)) if scale else dpad
+    nx = sum(c for _, c, _ in segments)
+    _timed("attention_short_keys", 4.0 * batch * heads * nq * (nk + nx) * d_true, lambda: _call("fmxi_attention_dual_f16", C.byref(a)),
+           tag=f"B={batch} H={heads} Nq={nq} Nk={nk}+{nx} d={dpad}", nbytes=2.0 * batch * heads * dpad * (2 * nq + 2 * nk))
+    return out
+
+
 def attention_single_head512(q, k, vt, out, *, batch, nq, nk, nk_pad, q_bs, q_rs, k_bs, k_rs, vt_bs, vt_ds, scale):
     """One 512-wide head, fused (fmx_attention_single_head512_f16 / _bf16): q / k token-major views, vt = V^T [512 rows][batch * nk_pad keys]."""
     sfx, _ = _elem(q, k, vt, out)
@@ -576,6 +618,16 @@ def add_control_(h, ctrl, alpha=1.0):
         ctrl = ctrl * alpha
     ctrl = ctrl.to(device=h.device, dtype=torch.float32).contiguous()
     _call("fmx_add_control_nchw", _p(h), _p(ctrl), b, c, hh * ww)
+    return h
+
+
+def add_scaled_(h, c, alpha=1.0):
+    """h += alpha * c on contiguous fp16 tensors of one shape (fmx_add_scaled_f16): native IP-Adapter's composite route adds a unit's attention
+    output to the text attention's with it.  Both 16-byte aligned."""
+    _check_f16(h, c)
+    if h.shape != c.shape or not (h.is_contiguous() and c.is_contiguous()) or h.data_ptr() % 16 or c.data_ptr() % 16:
+        raise ValueError(f"add_scaled_: {tuple(h.shape)} += {tuple(c.shape)} needs two contiguous, 16-byte aligned tensors of one shape")
+    _call("fmx_add_scaled_f16", _p(h), _p(c), 0, float(alpha), h.numel())
     return h
 
 

@@ -42,6 +42,11 @@ TINY_SD15_UNET_CONFIG = dict(
     context_dim=128, use_linear_in_transformer=False)
 # transformer_depth_output is consumed with pop() from the END (unet.py:649): listed low-res-last.
 
+# two heads per block at twice the width: heads of 64 and of 128.  Heads up to 64 wide are padded to 64 (backend/nn/unet.py _dpad), so the config
+# above never meets the wider kernels SD1.5's 80- and 160-wide heads run on; this one does at its lower level (128 -> 160: native IP-Adapter's
+# composite route)
+TINY_SD15_WIDE_HEADS_UNET_CONFIG = dict(TINY_SD15_UNET_CONFIG, model_channels=128, num_heads=2)
+
 TINY_SD15_INPAINT_UNET_CONFIG = dict(TINY_SD15_UNET_CONFIG, in_channels=9)  # 4 latent + 1 mask + 4 masked-image latent (sd-v1-5-inpainting)
 
 TINY_SDXL_UNET_CONFIG = dict(
@@ -237,6 +242,64 @@ def synth_lllite_state_dict(cfg, seed=21, gain=1.0, up_gain=1.0, **kw):
             if ".up.0." in k:
                 sd[k] = sd[k] * up_gain
     return sd
+
+
+IPADAPTER_CLIP_DIM = 64      # width of the synthetic CLIP-vision embeddings the tiny IP-Adapter files take
+
+
+def ipadapter_param_shapes(cfg, plus=False, clip_dim=IPADAPTER_CLIP_DIM, resampler_dim=128, depth=4):
+    """-> {"image_proj": name -> shape, "ip_adapter": name -> shape} of an IP-Adapter file for the UNet `cfg`: the base image projection (4
+    tokens) or, plus=True, the perceiver resampler (16 tokens, heads of 64), and a to_k_ip / to_v_ip pair per cross-attention, numbered 2n + 1 in
+    the reference's order (backend/nn/ipadapter.attn2_order)"""
+    from .backend.nn.ipadapter import attn2_order
+    from .backend.nn.layout import SpatialT, unet_layout
+    lay = unet_layout(cfg)
+    ctx = cfg["context_dim"]
+    proj = OrderedDict()
+    if plus:
+        proj["latents"] = (1, 16, resampler_dim)
+        proj["proj_in.weight"], proj["proj_in.bias"] = (resampler_dim, clip_dim), (resampler_dim,)
+        proj["proj_out.weight"], proj["proj_out.bias"] = (ctx, resampler_dim), (ctx,)
+        proj["norm_out.weight"], proj["norm_out.bias"] = (ctx,), (ctx,)
+        for i in range(depth):
+            p = f"layers.{i}."
+            for n in ("norm1", "norm2"):
+                proj[p + f"0.{n}.weight"], proj[p + f"0.{n}.bias"] = (resampler_dim,), (resampler_dim,)
+            proj[p + "0.to_q.weight"], proj[p + "0.to_kv.weight"] = (resampler_dim, resampler_dim), (2 * resampler_dim, resampler_dim)
+            proj[p + "0.to_out.weight"] = (resampler_dim, resampler_dim)
+            proj[p + "1.0.weight"], proj[p + "1.0.bias"] = (resampler_dim,), (resampler_dim,)
+            proj[p + "1.1.weight"], proj[p + "1.3.weight"] = (4 * resampler_dim, resampler_dim), (resampler_dim, 4 * resampler_dim)
+    else:
+        proj["proj.weight"], proj["proj.bias"] = (4 * ctx, clip_dim), (4 * ctx,)
+        proj["norm.weight"], proj["norm.bias"] = (ctx,), (ctx,)
+    width = {f"{L.key}.transformer_blocks.{di}": L.heads * L.dim_head for L in lay.all_layers() if isinstance(L, SpatialT) for di in range(L.depth)}
+    ip = OrderedDict()
+    for n, (_, _, _, name) in enumerate(attn2_order(lay)):
+        ip[f"{2 * n + 1}.to_k_ip.weight"] = ip[f"{2 * n + 1}.to_v_ip.weight"] = (width[name], ctx)
+    return {"image_proj": proj, "ip_adapter": ip}
+
+
+def synth_ipadapter_state_dict(cfg, plus=False, seed=31, gain=1.0, kv_gain=1.0, **kw):
+    """seeded IP-Adapter weights for the UNet `cfg`, in the layout of a .bin file: {"image_proj": {...}, "ip_adapter": {...}}.  The resampler's
+    LayerNorm in front of its feed-forward (`layers.N.1.0`) is drawn around 1 / 0 like every other norm; kv_gain scales to_k_ip / to_v_ip so that
+    a route that drops the image tokens computes something visibly else."""
+    shapes = ipadapter_param_shapes(cfg, plus=plus, **kw)
+    proj = synth_state_dict(shapes["image_proj"], seed=seed, gain=gain)
+    for k in proj:
+        if k.endswith((".1.0.weight", ".1.0.bias")):
+            proj[k] = synth_tensor("norm." + k, shapes["image_proj"][k], seed)
+    ip = synth_state_dict(shapes["ip_adapter"], seed=seed + 1, gain=gain * kv_gain)
+    return {"image_proj": proj, "ip_adapter": ip}
+
+
+def synth_clip_vision_embeds(plus=False, seed=41, clip_dim=IPADAPTER_CLIP_DIM, tokens=257):
+    """seeded stand-ins for the CLIP-vision outputs an IP-Adapter takes: (clip_embed, clip_embed_zeroed) -- image_embeds [1, D] and zeros for a base
+    file; penultimate_hidden_states [1, 257, D] and those of a black image (a second draw) for a plus file"""
+    g = torch.Generator().manual_seed(seed)
+    if not plus:
+        e = torch.randn(1, clip_dim, generator=g)
+        return e, torch.zeros_like(e)
+    return torch.randn(1, tokens, clip_dim, generator=g), torch.randn(1, tokens, clip_dim, generator=g) * 0.25
 
 
 def synth_controlnet_state_dict(cfg, hint_channels=3, seed=6, zero_conv_gain=1.0, **kw):

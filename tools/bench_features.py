@@ -16,6 +16,8 @@ batch sizes -- and what they cost.
                                                     patch at both strengths on the hooked executor, timed alternately in one process
     python tools/bench_features.py --only lllite     ControlNet-LLLite: plain / native (fused adapter kernel, captured graph) / the same unit as Python
                                                      attn1 / attn2 patches on the hooked executor, and the adapter launches on their own
+    python tools/bench_features.py --only ipadapter  IP-Adapter: plain / native with a base file, a plus file and two units (dual attention kernel,
+                                                     captured graph) / the composite route forced / the same units as Python attn2 replace patches
     python tools/bench_features.py --only taesd      the TAESD decode of batch x (res/8)^2 SDXL-shaped latents (synthetic weights, fp16) next to the Full
                                                      VAE decode of the same latents in the same process: median of 5 after warm-up, events around the calls
 """
@@ -554,6 +556,98 @@ def main():
                           "adapter_kernels_share_of_native_step": round(kernel_ms / med["lllite_native"], 4), "adapter_kernel_by_shape": by_shape,
                           "finite": finite, "shape": list(lat.shape)}), flush=True)
 
+    def ipadapter_leg(rounds=3):
+        """Plain; native IP-Adapter (transformer option "ipadapter": fmxi_attention_dual_f16 in place of the text attention of every cross-attention,
+        captured graph) with a base file (4 image tokens), a plus file (16) and both as two units; the composite route forced on the two-unit job
+        (text attention + one attention per unit and group + add_scaled, captured graph as well); and the two units as Python attn2 replace patches
+        on the eager hooked executor (backend/patcher/ipadapter.py python_patch) -- seeded weights, always on.  Primed once each, then timed
+        alternately, `rounds` jobs of a.steps steps per route in this one process, device events around each job.  Also one cross-attention launch
+        of each distinct shape on its own, dual against composite (device events, median of 20)."""
+        from forge_amd import hipops as ops
+        from forge_amd.backend.patcher import ipadapter as ipa
+        from forge_amd.backend.patcher.ipadapter import patch_ipadapter
+        base = eng.forge_objects.unet
+        files = {kind: synth.synth_ipadapter_state_dict(cfg, plus=kind == "plus", seed=31 if kind == "base" else 77, clip_dim=1280 if kind == "plus" else 1024,
+                                                        **({"resampler_dim": 1280} if kind == "plus" else {})) for kind in ("base", "plus")}
+        emb = {"base": synth.synth_clip_vision_embeds(False, clip_dim=1024), "plus": synth.synth_clip_vision_embeds(True, clip_dim=1280)}
+        one = lambda m, kind, w: patch_ipadapter(m, files[kind], emb[kind], w)  # noqa: E731
+        two = one(one(base, "base", 0.8), "plus", 0.5)
+        forced = one(one(base, "base", 0.8), "plus", 0.5)
+        for u in forced.model_options["transformer_options"]["ipadapter"]:
+            u.force_composite = True
+        python = ipa.install_python(base.clone(), one(one(base, "base", 0.8), "plus", 0.5).model_options["transformer_options"]["ipadapter"])
+        variants = {"plain": None, "ipadapter_native_base": one(base, "base", 0.8), "ipadapter_native_plus": one(base, "plus", 0.8),
+                    "ipadapter_native_two_units": two, "ipadapter_composite_two_units": forced, "ipadapter_python_two_units": python}
+        saved = eng.forge_objects_after_applying_lora
+        shapes = []
+        real_dual = ops.attention_dual
+        ops.attention_dual = lambda *x, **kw: (shapes.append((kw["batch"], kw["heads"], kw["nq"], kw["nk"], len(x[5]))), real_dual(*x, **kw))[1]
+
+        def once(unet, n):
+            if unet is not None:
+                eng.forge_objects_after_applying_lora = saved.shallow_copy()
+                eng.forge_objects_after_applying_lora.unet = unet
+            try:
+                pr = processing.StableDiffusionProcessingTxt2Img(sd_model=eng, c=c1, uc=u1, seed=1, sampler_name="Euler", batch_size=b, steps=n,
+                                                                 cfg_scale=7.0, width=width, height=height, do_decode=False)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                lat = processing.process_images(pr).latents
+                e1.record()
+                torch.cuda.synchronize()
+                return e0.elapsed_time(e1), lat
+            finally:
+                eng.forge_objects_after_applying_lora = saved
+                eng.forge_objects = saved.shallow_copy()
+        try:
+            for unet in variants.values():    # priming (arena, caches, graphs)
+                once(unet, 4)
+        finally:
+            ops.attention_dual = real_dual
+        ms = {k: [] for k in variants}
+        finite = True
+        for _ in range(rounds):
+            for k, unet in variants.items():
+                once(unet, 2)             # a job on another route came before: what follows a change of route is not timed
+                dt, lat = once(unet, a.steps)
+                ms[k].append(round(dt / a.steps, 2))
+                finite = finite and bool(torch.isfinite(lat).all())
+        med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+        # one cross-attention of each distinct two-unit shape on its own: the dual launch against the composite route's launches
+        net = eng.forge_objects.unet.model.diffusion_model
+        ctx = ipa.ipadapter_for_call(two.model_options["transformer_options"], 1.0, [1, 0], 2 * b, net)
+        fctx = ipa.ipadapter_for_call(forced.model_options["transformer_options"], 1.0, [1, 0], 2 * b, net)
+        by_shape = {}
+        for bu_, h_, nq_, nk_, nseg in sorted(set(s for s in shapes if s[4] == 2)):
+            blk = next(k for k, e in ctx.blocks.items() if e["xk"].shape[2] == h_ * 64)
+            q2 = torch.randn(bu_ * nq_, h_ * 64, device=dev).half()
+            kc = torch.randn(bu_ * 128, h_ * 64, device=dev).half()
+            vtc = torch.randn(h_ * 64, bu_ * 128, device=dev).half()
+            res = {}
+            for name, cx in (("dual", ctx), ("composite", fctx)):
+                times = []
+                for _ in range(23):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    net._cross_attention(blk, q2, kc, vtc, bu_, nq_, nk_, 128, h_, 64, cx)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    times.append(e0.elapsed_time(e1))
+                res[name + "_ms"] = round(sorted(times[3:])[10], 4)
+            res["launches_per_unet_call"] = sum(1 for s in [s for s in shapes if s[4] == 2][:len(ctx.blocks)] if s[:4] == (bu_, h_, nq_, nk_))
+            res["dual_GBps_q_plus_o"] = round(4.0 * bu_ * nq_ * h_ * 64 / res["dual_ms"] / 1e6, 1)
+            by_shape[f"B={bu_} H={h_} Nq={nq_} Nk={nk_}+20"] = res
+        print(json.dumps({"case": f"IP-Adapter (batch {b}, CFG 7: two groups): plain vs native (dual attention kernel, captured graph) with a base file, a plus "
+                                  "file and both vs the composite route forced vs the Python route (attn2 replace patches, eager hooked executor)",
+                          "sampler": "Euler", "steps": a.steps, "rounds": rounds, "ms_per_step": med, "ms_per_step_rounds": ms,
+                          "native_over_plain": {k: round(med[k] / med["plain"], 3) for k in med if k.startswith("ipadapter_native")},
+                          "python_over_native": round(med["ipadapter_python_two_units"] / med["ipadapter_native_two_units"], 3),
+                          "composite_over_dual": round(med["ipadapter_composite_two_units"] / med["ipadapter_native_two_units"], 3),
+                          "cross_attention_by_shape_two_units": by_shape, "finite": finite, "shape": list(lat.shape)}), flush=True)
+
+    if "ipadapter" in what:
+        ipadapter_leg()
     if "lllite" in what:
         lllite_leg()
     if "one" in what:
