@@ -534,12 +534,13 @@ def groupnorm(x, gamma, beta, eps, *, x1=None, silu=False, groups=32, out=None, 
 
 
 def layernorm(x, gamma, beta, eps=1e-5, out=None):
-    _check_f16(x, gamma, beta)
+    """LayerNorm over the last dim; fp16 or bf16 throughout"""
+    sfx, elem = _elem(x, gamma, beta, out)
     c = x.shape[-1]
     rows = x.numel() // c
     if out is None:
-        out = empty(x.shape, torch.float16, x.device)
-    _call("fmx_layernorm_f16", _p(x), _p(gamma), _p(beta), _p(out), rows, c, float(eps))
+        out = empty(x.shape, elem, x.device)
+    _call("fmx_layernorm" + sfx, _p(x), _p(gamma), _p(beta), _p(out), rows, c, float(eps))
     return out
 
 
@@ -556,11 +557,11 @@ def rmsnorm(x, weight, eps=1e-6, out=None):
 
 def layernorm_padded(x, gamma, beta, out, rows_per_image, eps=1e-5):
     """LayerNorm of x [B*n, C] written into out [B, n_pad, C] (rows n..n_pad of every image are left untouched)."""
-    _check_f16(x, gamma, beta, out)
+    sfx, _ = _elem(x, gamma, beta, out)
     c = x.shape[-1]
     rows = x.numel() // c
     assert out.is_contiguous() and out.shape[-1] == c and out.shape[0] * rows_per_image == rows and out.shape[1] >= rows_per_image
-    _call("fmx_layernorm_padded_f16", _p(x), _p(gamma), _p(beta), _p(out), rows, c, float(eps), rows_per_image, out.shape[1])
+    _call("fmx_layernorm_padded" + sfx, _p(x), _p(gamma), _p(beta), _p(out), rows, c, float(eps), rows_per_image, out.shape[1])
     return out
 
 

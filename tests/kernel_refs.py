@@ -1,5 +1,6 @@
 """fp64 references and ulp tolerances shared by the kernel-level parity tests (tests/test_gpu_kernels_bf16.py, tests/test_gpu_small_kernels.py,
-tests/test_gpu_gemm_windows.py, tests/test_gpu_vae_direct.py, tests/test_gpu_sampler_kernels.py, tests/test_gpu_groupnorm_routes.py) and their CPU companion (tests/test_kernel_ref_teeth.py), which plants one plausible bug into each reference and checks that the GPU tests'
+tests/test_gpu_gemm_windows.py, tests/test_gpu_vae_direct.py, tests/test_gpu_sampler_kernels.py, tests/test_gpu_groupnorm_routes.py,
+tests/test_gpu_token_kernels.py) and their CPU companion (tests/test_kernel_ref_teeth.py), which plants one plausible bug into each reference and checks that the GPU tests'
 tolerance would reject it.
 
 Discipline: every reference is the same operation in fp64 on the kernel's own rounded inputs (the fp16 / bf16 tensors it read, upcast).
@@ -960,3 +961,141 @@ def gn_apply_emul(x, table, silu, dtype):
     """y = x scale + shift (+ SiLU) in fp32, rounded once: x [n, hw, C] -> the same shape in `dtype`"""
     y = x.float() * table[:, None, :, 0] + table[:, None, :, 1]
     return (y * torch.sigmoid(y) if silu else y).to(dtype)
+
+
+# ---- the token-path row norms and the q/k norm + rope kernel (tests/test_gpu_token_kernels.py) -----------------------------------------------------
+# fmx_layernorm / _padded / _mod and fmx_rmsnorm (csrc/fmx_norm.hip: ln_kernel<MAXOCT, MOD>, rmsnorm_kernel<MAXOCT>), fmx_flux_qk_norm_rope
+# (csrc/fmx_flux.hip).  `eps` reaches the kernels as a C `float`: the tests hand f32(eps) to the references.
+#
+# LN_TOL (LayerNorm, its padded and its modulated form): the form of GN_TOL.  The kernel keeps the row in registers, takes the mean and then the sum of
+# (x - mean)^2 in fp32 (two passes: no E[x^2] - mean^2 cancellation), forms d * rstd * ((MOD ? 1 : 0) + g) + b in fp32 and rounds ONCE: 0.5 ulp of the
+# result plus a handful of fp32 roundings (2^-24 relative each) of terms no larger than |d rstd g| + |b|.  The floor, one ulp at 1.0, is for results
+# near zero -- (1 + scale) ~ 0, or d rstd g ~ -b -- whose error comes from the fp32 mean and rstd acting on terms of magnitude ~1, not from their own
+# rounding.  A large common offset costs nothing: 16-bit inputs at offset 30000 are multiples of 16 (fp16) or 128 (bf16), far coarser than the fp32
+# mean's rounding, so d is exact or nearly so.
+LN_TOL = {torch.bfloat16: (1.0, EPS[torch.bfloat16]), torch.float16: (1.0, EPS[torch.float16])}
+# RMS_TOL (T5 RMS norm): fp32 sum of squares / c (relative ~1e-6 whatever the order: every term is >= 0), rsqrtf, two fp32 products, one rounding:
+# ELEM_TOL as it stands -- 1 ulp with the floor at the smallest subnormal step.  Nothing cancels, so there is no floor at the scale of 1.
+RMS_TOL = dict(ELEM_TOL)
+# ROPE_TOL (per-head RMS norm of q and k over 128 + rotation of interleaved pairs): about six fp32 roundings and rsqrtf on the way to the two products
+# cos a and sin b, each of magnitude at most sqrt(128) |scale| ~ 12: ~1e-5 absolute at the very most, then one rounding of the result: 1 ulp.  The
+# floor, one ulp at 1.0 (1e-3 in fp16), is there because cos a - sin b cancels: a result near zero carries the fp32 error of its two terms.
+ROPE_TOL = {torch.bfloat16: (1.0, EPS[torch.bfloat16]), torch.float16: (1.0, EPS[torch.float16])}
+#
+# Worst excess (units of the tolerance) over every case of tests/test_gpu_token_kernels.py, fp16 / bf16: the emulations below (the kernels' arithmetic in
+# plain fp32 torch; tests/test_kernel_ref_teeth.py asserts <= 1 and prints them) and the worst `MEASURED` line of the GPU file on MI355X:
+#   kernel               tolerance    emulation        MI355X
+#   layernorm            LN_TOL       0.408 / 0.437    0.408 / 0.437
+#   layernorm_padded     LN_TOL       0.379 / 0.406    0.379 / 0.406
+#   layernorm_mod        LN_TOL       0.443 / 0.452    0.443 / 0.452
+#   rmsnorm              RMS_TOL      0.500 / 0.500    0.500 / 0.500
+#   flux_qk_norm_rope    ROPE_TOL     0.391 / 0.389    0.391 / 0.389     (V^T: bit-equal)
+# (No MI355X figure differs from its emulation in the third digit: the worst elements are half-ulp roundings of the result, which neither the device's
+# rsqrtf nor the wave's order of summation moves.  rmsnorm's 0.500 is that single rounding with nothing else in the way.)
+# Smallest excess of each planted bug over the cases on which tests/test_kernel_ref_teeth.py requires it to show (>= 4 asserted), fp16 / bf16:
+#   layernorm          eps_outside_sqrt 1380 / 172 (ONLY on tables with a row of spread 1e-3), last_octet_skipped 1230 / 154 (every table of >= 5 rows)
+#   layernorm_mod      eps_outside_sqrt 584 / 74, scale_shift_swapped 5230 / 914, batch0_vectors 5030 / 1140, one_plus_dropped 3170 / 861,
+#                      last_octet_skipped 2640 / 321 (every plant on every case)
+#   rmsnorm            mean_subtracted 83000 / 48900 and last_octet_skipped 4600 / 3700 (tables with the outlier row), eps_outside_sqrt 798 / 101 (tables
+#                      with a row of scale < 1e-2)
+#   flux_qk_norm_rope  sin_sign 2400 / 298, half_split 1930 / 242, k_uses_q_scale 414 / 52 (every launch), row_off_dropped 3040 / 378 (row_off > 0),
+#                      eps_outside_sqrt 212 / 26 (ONLY through token rows of magnitude < 1e-2), rms_over_all_heads 130 / 16 (more than one token)
+
+
+def layernorm_mod_ref(x, scale, shift, rows_per_batch, eps):
+    """fmx_layernorm_mod: (1 + scale[b]) * LN(x, no affine) + shift[b], b = row // rows_per_batch.  x [rows, c], scale / shift [B, c] -> fp64"""
+    img = torch.arange(x.shape[0]) // rows_per_batch
+    return (1.0 + scale.double()[img]) * F.layer_norm(x.double(), (x.shape[-1],), None, None, eps) + shift.double()[img]
+
+
+def rmsnorm_ref(x, w, eps):
+    x = x.double()
+    return x * torch.rsqrt((x * x).mean(-1, keepdim=True) + eps) * w.double()
+
+
+def _rope_split(qkv, b, l, h):
+    """qkv [b * l, >= 3 * h * 128] (any row stride) -> q, k, v as [b, l, h, 128] views of the same element type"""
+    x = qkv[:, :3 * h * 128].reshape(b, l, 3, h, 128)
+    return x[:, :, 0], x[:, :, 1], x[:, :, 2]
+
+
+def qk_norm_rope_ref(qkv, q_scale, k_scale, pe, b, l, h, row_off, eps):
+    """fmx_flux_qk_norm_rope in fp64: per-head RMS norm over 128 (eps inside the root) times the scale vector, then the rotation of the INTERLEAVED pairs
+    (2i, 2i + 1) by pe[row_off + t, i] = (cos, sin).  qkv [b * l, >= 3 h 128], pe fp32 [>= row_off + l, 64, 2] -> (q, k) fp64 [b, l, h, 128]"""
+    q, k, _ = _rope_split(qkv.double(), b, l, h)
+    cs = pe[row_off:row_off + l].double()[None, :, None]                    # [1, l, 1, 64, 2]
+
+    def one(t, s):
+        t = t * torch.rsqrt((t * t).mean(-1, keepdim=True) + eps) * s.double()
+        a, bb = t[..., 0::2], t[..., 1::2]
+        return torch.stack([cs[..., 0] * a - cs[..., 1] * bb, cs[..., 1] * a + cs[..., 0] * bb], -1).reshape(b, l, h, 128)
+
+    return one(q, q_scale), one(k, k_scale)
+
+
+def _rstd_emul(ms, eps, plant):
+    e = torch.tensor(eps, dtype=torch.float32)
+    return 1.0 / (torch.sqrt(ms) + e) if plant == "eps_outside_sqrt" else torch.rsqrt(ms + e)
+
+
+def ln_emul(x, gamma, beta, eps, dtype, rows_per_batch=None, plant=None):
+    """ln_kernel in fp32 torch: mean = sum / c, variance = sum (x - mean)^2 / c (two passes), d * rstd * ((MOD ? 1 : 0) + g) + b, rounded once.
+    rows_per_batch None: gamma / beta [c] (MOD = false); else MOD = true with gamma = scale [B, c], beta = shift [B, c].
+    plant: None or one bug -- "eps_outside_sqrt" (1 / (sqrt(var) + eps)), "last_octet_skipped" (the last 8 channels of a row left out of both sums), and
+    for MOD "scale_shift_swapped", "batch0_vectors" (every row uses batch 0's vectors), "one_plus_dropped" (scale * LN + shift)"""
+    xf = x.float()
+    c = xf.shape[-1]
+    part = (lambda t: t[:, :c - 8]) if plant == "last_octet_skipped" else (lambda t: t)
+    mean = part(xf).sum(-1, keepdim=True) / float(c)
+    d = xf - mean
+    rstd = _rstd_emul((part(d) * part(d)).sum(-1, keepdim=True) / float(c), eps, plant)
+    if rows_per_batch is None:
+        g, bt, one = gamma.float(), beta.float(), 0.0
+    else:
+        img = torch.arange(xf.shape[0]) // rows_per_batch
+        if plant == "batch0_vectors":
+            img = torch.zeros_like(img)
+        g, bt, one = gamma.float()[img], beta.float()[img], 0.0 if plant == "one_plus_dropped" else 1.0
+        if plant == "scale_shift_swapped":
+            g, bt = bt, g
+    return (d * rstd * (one + g) + bt).to(dtype)
+
+
+def rmsnorm_emul(x, w, eps, dtype, plant=None):
+    """rmsnorm_kernel in fp32 torch: sum of squares / c, x * rstd * w, rounded once.  plant: None or one bug -- "mean_subtracted" (LayerNorm's statistics
+    and numerator), "eps_outside_sqrt", "last_octet_skipped" (the last 8 channels left out of the sum of squares)"""
+    xf = x.float()
+    c = xf.shape[-1]
+    if plant == "mean_subtracted":
+        xf = xf - xf.sum(-1, keepdim=True) / float(c)
+    sq = xf * xf
+    if plant == "last_octet_skipped":
+        sq = sq[:, :c - 8]
+    return (xf * _rstd_emul(sq.sum(-1, keepdim=True) / float(c), eps, plant) * w.float()).to(dtype)
+
+
+def qk_norm_rope_emul(qkv, q_scale, k_scale, pe, b, l, h, row_off, eps, dtype, plant=None):
+    """qk_norm_rope_kernel in fp32 torch, as the source has it: one pair per lane, rsqrtf(wave_sum(x0^2 + x1^2) * (1 / 128) + eps), x * r * scale, the
+    rotation in fp32, one rounding.  -> (q, k) [b, l, h, 128] in `dtype`.  plant: None or one bug -- "sin_sign", "half_split" (pairs (i, i + 64): the
+    rotate-half convention), "row_off_dropped" (pe[t], not pe[row_off + t]), "k_uses_q_scale", "eps_outside_sqrt", "rms_over_all_heads" (one RMS
+    per token over h * 128)"""
+    q, k, _ = _rope_split(qkv.float(), b, l, h)
+    off = 0 if plant == "row_off_dropped" else row_off
+    cs = pe[off:off + l].float()[None, :, None]
+    cos, sin = cs[..., 0], -cs[..., 1] if plant == "sin_sign" else cs[..., 1]
+
+    def one(t, s):
+        sq = t * t
+        pair = sq[..., 0::2] + sq[..., 1::2]
+        if plant == "rms_over_all_heads":
+            ms = pair.sum((-1, -2), keepdim=True) * (1.0 / (128.0 * h))
+        else:
+            ms = pair.sum(-1, keepdim=True) * (1.0 / 128.0)
+        t = t * _rstd_emul(ms, eps, plant) * s.float()
+        if plant == "half_split":
+            a, bb = t[..., :64], t[..., 64:]
+            return torch.cat([cos * a - sin * bb, sin * a + cos * bb], -1).to(dtype)
+        a, bb = t[..., 0::2], t[..., 1::2]
+        return torch.stack([cos * a - sin * bb, sin * a + cos * bb], -1).reshape(b, l, h, 128).to(dtype)
+
+    return one(q, q_scale), one(k, q_scale if plant == "k_uses_q_scale" else k_scale)

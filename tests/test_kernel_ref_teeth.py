@@ -1,5 +1,5 @@
 """CPU: the kernel-level GPU tests have teeth.  For each test in tests/test_gpu_kernels_bf16.py, tests/test_gpu_small_kernels.py, each test
-family of tests/test_gpu_attention_generic.py, each window case of tests/test_gpu_gemm_windows.py, each check of tests/test_gpu_vae_direct.py, each kernel of tests/test_gpu_sampler_kernels.py and each part of tests/test_gpu_groupnorm_routes.py, one
+family of tests/test_gpu_attention_generic.py, each window case of tests/test_gpu_gemm_windows.py, each check of tests/test_gpu_vae_direct.py, each kernel of tests/test_gpu_sampler_kernels.py, each part of tests/test_gpu_groupnorm_routes.py and each kernel of tests/test_gpu_token_kernels.py, one
 plausible subtle bug is planted into the fp64 reference (tests/kernel_refs.py) and evaluated on that test's own inputs; the planted result must
 lie outside the GPU test's tolerance by at least 4x (kernel_refs.excess >= 4), or -- for the exact tests -- differ in at least 4 places.
 Runs without a GPU, so a tolerance too loose to catch anything fails before anyone gets a GPU."""
@@ -1196,3 +1196,180 @@ def test_gn_routes_case_list_reaches_both_folds_and_every_lane_layout():
     octs = [c // 8 for c in N.STATS_C]
     assert any(o < 256 and 256 % o for o in octs) and 256 in octs and any(o > 256 for o in octs) and 1 in octs
     assert all(any(nch > hw for c, h, nch in N.STATS_CASES if h == hw) for hw in N.STATS_HW)
+
+
+# ---- the token-path row norms and the q/k norm + rope kernel (tests/test_gpu_token_kernels.py) -----------------------------------------------------
+# kernel_refs.ln_emul / rmsnorm_emul / qk_norm_rope_emul (the kernels' arithmetic in plain fp32 torch) run on every case of the GPU file: unplanted they stay
+# inside LN_TOL / RMS_TOL / ROPE_TOL (worst excess printed: the table in kernel_refs.py), every planted bug leaves the tolerance by >= 4x on the cases named
+# for it, and no fp64 reference leaves the range of the output type.
+import test_gpu_token_kernels as T  # noqa: E402
+
+
+def _finite(want, dtype, what):
+    assert bool(torch.isfinite(want.to(dtype)).all()), f"{what}: the fp64 reference overflows {dtype}"
+
+
+def _plant_report(kernel, dtype, worst, plants):
+    """worst: the unplanted emulation's worst excess; plants: {plant: (its SMALLEST excess over the cases it has to show on, that case)}"""
+    print(f"EMULATION {kernel} {_DT_NAME[dtype]}: {worst:.3f}")
+    assert worst <= 1.0, f"{kernel} {dtype}: the unplanted fp32 emulation is {worst:.3g}x the tolerance"
+    for plant, (e, case) in plants.items():
+        print(f"PLANT {kernel} {_DT_NAME[dtype]} {plant}: {e:.3g} ({case})")
+        assert e >= TEETH, f"{kernel} {dtype} {plant}: the planted bug is only {e:.3g}x the tolerance on {case}"
+
+
+def _weakest(plants, plant, e, case):
+    if e < plants.get(plant, (math.inf, None))[0]:
+        plants[plant] = (e, case)
+
+
+def _has_small_row(idx):
+    return T.SMALL_PAIR in idx
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_token_layernorm_emulation_and_planted_bugs(dtype):
+    """eps outside the root shows ONLY on rows of spread 1e-3 (variance ~ eps): it must bite on every table that has such a row.  The last octet left out of the
+    statistics must bite at every width on every table of 5 rows or more (at c = 8 nothing is left to sum)"""
+    worst, plants = {"layernorm": 0.0, "layernorm_padded": 0.0}, {}
+    cases = [(f"layernorm rows={rows},c={c}", T.ln_case(rows, c, dtype), T.ln_want(rows, c, dtype), T.pair_of_row(rows, T.LN_C.index(c))) for rows, c in T.LN_CASES]
+    cases += [(f"layernorm_padded c={c}", T.pad_case(c, dtype), T.pad_want(c, dtype), T.pair_of_row(T.PAD_B * T.PAD_N, c % 7)) for c in T.PAD_C]
+    for what, (x, gamma, beta), want, idx in cases:
+        _finite(want, dtype, what)
+        eps = R.f32(T.LN_EPS)
+        worst[what.split()[0]] = max(worst[what.split()[0]], R.excess(R.ln_emul(x, gamma, beta, eps, dtype), want, dtype, *R.LN_TOL[dtype]))
+        e = R.excess(R.ln_emul(x, gamma, beta, eps, dtype, plant="last_octet_skipped"), want, dtype, *R.LN_TOL[dtype])
+        if x.shape[0] >= 5:
+            assert e >= TEETH, f"{what}: last octet skipped is only {e:.3g}x"
+            _weakest(plants, "last_octet_skipped", e, what)
+            assert torch.equal(want[T.CONST_ROW], beta.double()) and torch.equal(want[T.ZERO_ROW], beta.double())      # a constant row's result is beta
+        e = R.excess(R.ln_emul(x, gamma, beta, eps, dtype, plant="eps_outside_sqrt"), want, dtype, *R.LN_TOL[dtype])
+        if _has_small_row(idx) and not (x.shape[0] >= 5 and idx.index(T.SMALL_PAIR) in (T.CONST_ROW, T.ZERO_ROW) and idx.count(T.SMALL_PAIR) == 1):
+            assert e >= TEETH, f"{what}: eps outside the root is only {e:.3g}x although the table has a row of spread 1e-3"
+            _weakest(plants, "eps_outside_sqrt", e, what)
+    _plant_report("layernorm_padded", dtype, worst["layernorm_padded"], {})
+    _plant_report("layernorm", dtype, worst["layernorm"], plants)
+    assert set(plants) == {"last_octet_skipped", "eps_outside_sqrt"}
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_token_layernorm_mod_emulation_and_planted_bugs(dtype):
+    """every MOD plant must bite on EVERY case: the vectors differ per batch and between scale and shift, and 1 + scale differs from scale everywhere"""
+    worst, plants = 0.0, {}
+    for c, rpb, win in T.MOD_CASES:
+        what = f"layernorm_mod c={c},rows_per_batch={rpb},window={win}"
+        x, mods, sc, sh = T.mod_case(c, rpb, win, dtype)
+        scale, shift = T.mod_vectors(mods, c, sc, sh)
+        want = T.mod_want(c, rpb, win, dtype)
+        _finite(want, dtype, what)
+        assert (T.MOD_B * rpb) % 4 != 0 or rpb % 4 != 0                                        # blocks of four rows straddle the batches
+        assert float((1.0 + scale[T.MOD_NEG_BATCH, :c // 4].double()).abs().max()) < 0.02       # the quarter where the floor is what holds
+        eps = R.f32(T.MOD_EPS)
+        worst = max(worst, R.excess(R.ln_emul(x, scale, shift, eps, dtype, rows_per_batch=rpb), want, dtype, *R.LN_TOL[dtype]))
+        for plant in ("eps_outside_sqrt", "scale_shift_swapped", "batch0_vectors", "one_plus_dropped", "last_octet_skipped"):
+            e = R.excess(R.ln_emul(x, scale, shift, eps, dtype, rows_per_batch=rpb, plant=plant), want, dtype, *R.LN_TOL[dtype])
+            assert e >= TEETH, f"{what} {plant}: only {e:.3g}x"
+            _weakest(plants, plant, e, what)
+        # the wrong chunk of the buffer (6e4 everywhere) in place of scale
+        for k in [k for k in range(T.MOD_WINDOWS[win][0]) if k not in (sc, sh)][:1]:
+            e = R.excess(R.ln_emul(x, mods[:, k * c:(k + 1) * c], shift, eps, dtype, rows_per_batch=rpb), want, dtype, *R.LN_TOL[dtype])
+            assert e >= TEETH, f"{what}: scale read from chunk {k} is only {e:.3g}x"
+    _plant_report("layernorm_mod", dtype, worst, plants)
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_token_rmsnorm_emulation_and_planted_bugs(dtype):
+    """eps outside the root shows only on rows of scale <~ 1e-2 (mean square ~ eps): every table with more than one row has one, and the one-row tables at
+    scale 1e-3.  The mean subtracted and the last octet left out of the sum must show wherever a row has its outlier channel, which sits in the last octet
+    (eight ordinary channels out of 4096 move rstd by 0.1%: a quarter of a bf16 ulp, so without the outlier the wide bf16 rows could not show it)"""
+    worst, plants = 0.0, {}
+    for rows, c in T.RMS_CASES:
+        what = f"rmsnorm rows={rows},c={c}"
+        x, w = T.rms_case(rows, c, dtype)
+        want = T.rms_want(rows, c, dtype)
+        _finite(want, dtype, what)
+        scales = T.rms_scales(rows, c)
+        eps = R.f32(T.RMS_EPS)
+        worst = max(worst, R.excess(R.rmsnorm_emul(x, w, eps, dtype), want, dtype, *R.RMS_TOL[dtype]))
+        if rows >= 5:
+            assert scales.count(0.0) == 1 and not bool(want[scales.index(0.0)].any()) and max(scales) > 299.0 and 0.0 < min(s for s in scales if s) < 1.1e-3
+        for plant in ("mean_subtracted", "eps_outside_sqrt", "last_octet_skipped"):
+            e = R.excess(R.rmsnorm_emul(x, w, eps, dtype, plant=plant), want, dtype, *R.RMS_TOL[dtype])
+            must = {"mean_subtracted": max(scales) > 299.0, "eps_outside_sqrt": 0.0 < min(s for s in scales if s) < 1e-2, "last_octet_skipped": max(scales) > 299.0}[plant]
+            if must:
+                assert e >= TEETH, f"{what} {plant}: only {e:.3g}x"
+                _weakest(plants, plant, e, what)
+    _plant_report("rmsnorm", dtype, worst, plants)
+    assert len(plants) == 3
+
+
+_ROPE_ALL_CASES = ("sin_sign", "half_split", "k_uses_q_scale", "eps_outside_sqrt")
+
+
+@pytest.mark.parametrize("dtype", DTS)
+def test_token_qk_norm_rope_emulation_and_planted_bugs(dtype):
+    """the sign of sin, the rotate-half convention and k normalised with q's scale must bite on every launch of every case; eps outside the root shows ONLY on
+    token rows of magnitude <~ 1e-2 and must bite on every launch that has one (all with more than 8 tokens in the batch); pe[t] for pe[row_off + t] on every
+    launch with row_off > 0; one RMS per token over all heads shows through the heads' own chi-square spread (~6% of an element) on every launch with more
+    than one token"""
+    worst, plants = 0.0, {}
+    for name, (b, h, l_pad, launches, window) in T.ROPE_CASES.items():
+        pe, Ls = T.rope_case(name, dtype)
+        eps = R.f32(T.ROPE_EPS)
+        for L, (wq, wk) in zip(Ls, T.rope_want(name, dtype)):
+            what = f"{name} tokens={L['tokens']}@{L['row_off']}"
+            _finite(wq, dtype, what)
+            _finite(wk, dtype, what)
+            args = (L["qkv"], L["qs"], L["ks"], pe, b, L["tokens"], h, L["row_off"], eps, dtype)
+
+            def ex(plant=None):
+                q, k = R.qk_norm_rope_emul(*args, plant=plant)
+                return max(R.excess(q, wq, dtype, *R.ROPE_TOL[dtype]), R.excess(k, wk, dtype, *R.ROPE_TOL[dtype]))
+
+            worst = max(worst, ex())
+            rms = L["qkv"].double().pow(2).mean(-1).sqrt()
+            must = {p: True for p in ("sin_sign", "half_split", "k_uses_q_scale")}
+            must["eps_outside_sqrt"] = bool(((rms > 0) & (rms < 1e-2)).any())
+            must["row_off_dropped"] = L["row_off"] > 0
+            must["rms_over_all_heads"] = b * L["tokens"] > 2
+            for plant, m in must.items():
+                if m:
+                    e = ex(plant)
+                    assert e >= TEETH, f"{what} {plant}: only {e:.3g}x"
+                    _weakest(plants, plant, e, what)
+            if window:
+                assert L["qkv"].stride(0) == 3 * h * T.D + T.ROPE_WINDOW[1] and float(L["buf"][0, 0]) > 5e4 and float(L["buf"][0, -1]) > 5e4
+    _plant_report("flux_qk_norm_rope", dtype, worst, plants)
+    assert len(plants) == 6
+
+
+def test_token_rope_cases_reach_every_store_path():
+    """conditions of the GPU file, from the kernel's store rule restated (a 32-token half is stored as four 16-byte vectors iff it is full and its first column
+    is a multiple of 8 elements, else element by element): the case list has vector halves, FULL halves on the scalar path at 8-byte and at 2-byte alignment,
+    ragged halves, empty halves, and pad columns behind the last token; the rope ids differ for every token"""
+    seen = set()
+    for name, (b, h, l_pad, launches, window) in T.ROPE_CASES.items():
+        for tokens, row_off in launches:
+            assert l_pad >= row_off + tokens
+            for bi in range(b):
+                for t0 in range(0, tokens, 64):
+                    for half in (0, 1):
+                        valid = min(32, tokens - (t0 + half * 32))
+                        col = bi * l_pad + row_off + t0 + half * 32
+                        align = 8 if col % 8 == 0 else 4 if col % 4 == 0 else 1
+                        seen.add(("empty",) if valid <= 0 else ("full" if valid == 32 else "ragged", align))
+        covered = max(t + o for t, o in launches)
+        seen.add(("pad", l_pad > covered))
+    assert {("full", 8), ("full", 4), ("full", 1), ("ragged", 8), ("ragged", 1), ("empty",), ("pad", True), ("pad", False)} <= seen, seen
+    pe = T.rope_pe(138)
+    assert len({tuple(r.tolist()) for r in pe.reshape(138, -1)}) == 138
+
+
+def test_token_norm_widths_sit_on_every_dispatch_threshold():
+    """launch_ln: MAXOCT 1 / 2 / 3 / 8 at c / 8 <= 64 / 128 / 192 / else; fmx_rmsnorm: 1 / 2 / 4 / 8 at 64 / 128 / 256 / else -- each threshold has the width on
+    it and the next one up, and no row count fills its last block"""
+    for widths, thr in ((T.LN_C, (64, 128, 192)), (T.RMS_C, (64, 128, 256))):
+        for t in thr:
+            assert 8 * t in widths and 8 * t + 8 in widths
+        assert 8 in widths and 4096 in widths
+    assert all(r % 4 for r in T.ROWS) and all((T.MOD_B * rpb) % 4 for _, rpb, _ in T.MOD_CASES) and (T.PAD_B * T.PAD_N) % 4

@@ -27,8 +27,6 @@ ALLOWED = {
     "fmx_event_record": "timing helper of the launch profiler, no arithmetic",
     "fmx_event_elapsed_ms": "timing helper of the launch profiler, no arithmetic",
     "fmx_event_destroy": "timing helper of the launch profiler, no arithmetic",
-    "fmx_layernorm_bf16": "exported bf16 twin with no Python route (hipops.layernorm is fp16 only)",
-    "fmx_layernorm_padded_bf16": "exported bf16 twin with no Python route (hipops.layernorm_padded is fp16 only)",
 }
 
 
@@ -85,6 +83,7 @@ def test_wrapper_map_sees_the_dtype_dispatch():
     assert {"fmx_timestep_embedding", "fmx_timestep_embedding_bf16"} <= wraps["timestep_embedding"]
     assert "fmx_groupnorm_stats_bf16" in wraps["groupnorm"]            # through groupnorm_stats
     assert "fmx_gemm_conv_f16" in wraps["linear"]                       # through conv_gemm
+    assert {"fmx_layernorm_f16", "fmx_layernorm_bf16"} <= wraps["layernorm"]
 
 
 def test_every_entry_point_has_a_gpu_test():
