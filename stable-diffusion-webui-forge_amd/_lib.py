@@ -1,4 +1,4 @@
-"""ctypes binding of libfmx_gfx950.so (C-ABI declared in include/fmx.h; include/fmx_ext.h, include/fmx_lllite.h and include/fmx_ipadapter.h hold entry points not yet declared there).
+"""ctypes binding of libfmx_gfx950.so (C-ABI declared in include/fmx.h; include/fmx_ext.h, include/fmx_lllite.h, include/fmx_ipadapter.h and include/fmx_clipvision.h hold entry points not yet declared there).
 
 The library is built in-tree by `build()` (hipcc --offload-arch=gfx950) so that it travels with the
 repo snapshot.  There is deliberately NO fallback: if the shared object is missing or a symbol is
@@ -48,7 +48,7 @@ HEADER = os.path.join(_HERE, "..", "include", "fmx.h")
 _SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64,
             "float": C.c_float, "double": C.c_double}
 _STRUCT_NAMES = {"fmx_gemm_args": "GemmArgs", "fmx_attn_args": "AttnArgs", "fmx_conv_gn_args": "ConvGnArgs"}
-_HEADER_OF_PREFIX = {"fmx_": "fmx.h", "fmxe_": "fmx_ext.h", "fmxl_": "fmx_lllite.h", "fmxi_": "fmx_ipadapter.h"}
+_HEADER_OF_PREFIX = {"fmx_": "fmx.h", "fmxe_": "fmx_ext.h", "fmxl_": "fmx_lllite.h", "fmxi_": "fmx_ipadapter.h", "fmxv_": "fmx_clipvision.h"}
 _PARAM = re.compile(r"(?:const )?(\w+) ?((?:\* ?(?:const ?)?)*)(\w+)?")
 
 
@@ -147,6 +147,9 @@ LlliteSlot = _lllite_structs["fmxl_lllite_slot"]
 IPADAPTER_HEADER = os.path.join(_HERE, "..", "include", "fmx_ipadapter.h")
 IPADAPTER_SIGNATURES, _, _ipadapter_structs, IPADAPTER_CONSTANTS = parse_header(_read_header(IPADAPTER_HEADER), prefix="fmxi_", known_structs=_structs)
 DualAttnArgs = _ipadapter_structs["fmxi_dual_attn_args"]
+# the two CLIP-vision front-end entry points of include/fmx_clipvision.h (prefix fmxv_; that header says why they are in none of the other four)
+CLIPVISION_HEADER = os.path.join(_HERE, "..", "include", "fmx_clipvision.h")
+CLIPVISION_SIGNATURES, _, _, CLIPVISION_CONSTANTS = parse_header(_read_header(CLIPVISION_HEADER), prefix="fmxv_", known_structs=_structs)
 
 
 def source_tree_hash():
@@ -213,7 +216,7 @@ def lib():
             raise FmxError(f"{LIB_PATH} not found: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(hipcc --offload-arch=gfx950).  There is no CPU/PyTorch fallback by design.")
         handle = C.CDLL(LIB_PATH)
-        for name, argtypes, restype in [(n, a, C.c_int) for n, a in {**SIGNATURES, **EXT_SIGNATURES, **LLLITE_SIGNATURES, **IPADAPTER_SIGNATURES}.items()] + [(n, [], C.c_char_p) for n in ACCESSORS]:
+        for name, argtypes, restype in [(n, a, C.c_int) for n, a in {**SIGNATURES, **EXT_SIGNATURES, **LLLITE_SIGNATURES, **IPADAPTER_SIGNATURES, **CLIPVISION_SIGNATURES}.items()] + [(n, [], C.c_char_p) for n in ACCESSORS]:
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:

@@ -13,7 +13,8 @@ existing kernels.  Both stay on the captured graph.  `python_patch` is the same 
 hooked executor runs where the native route does not apply, and what tests and tools/bench_features.py compare against.
 
 Weight types: "original" scales the unit's term (the segment weight); "linear" and "channel" are transformations of the unit's K / V, done once
-when the unit is prepared, with segment weight 1.  The CLIP-vision encoder is out of scope: `embeds` are its outputs, handed in by the caller."""
+when the unit is prepared, with segment weight 1.  `embeds` are the CLIP-vision encoder's outputs, handed in by the caller or computed from an
+image by backend/patcher/clipvision.ClipVisionModel (embeds_from_image), once per job and before any graph."""
 import math
 
 import torch
@@ -326,10 +327,47 @@ def _has_foreign_hooks(to):
     return Net._hooks(rest) is not None
 
 
-def patch_ipadapter(unet_patcher, ipadapter_sd, embeds, weight, weight_type="original", start_at=0.0, end_at=1.0, attn_mask=None, unfold_batch=False):
+PREPROCESSOR_KEYS = ("clip_vision", "image", "weight_type", "noise", "embeds", "unfold_batch")
+
+
+def file_clip_width(model, info):
+    """the file's clip_embeddings_dim: the input width of its image projection"""
+    return int(model["image_proj"]["proj_in.weight" if info["is_plus"] else "proj.weight"].shape[1])
+
+
+def embeds_from_image(clip_vision, image, model, info, noise=0.0):
+    """(clip_embed, clip_embed_zeroed) as apply_ipadapter computes them from an image (IPAdapterPlus.py:686-702): plus files take
+    penultimate_hidden_states of the image and of a black 224 x 224 image (zeroed_hidden_states), base files image_embeds and zeros.  The image
+    and the black image go through the tower in ONE batch.  clip_vision: backend/patcher/clipvision.ClipVisionModel."""
+    if (noise or 0) > 0:
+        raise NotImplementedError(f"{FEATURE}: noise {noise} > 0: the reference's image_add_noise is torchvision's ElasticTransform on a reseeded "
+                                  "generator, which has no counterpart here; pass noise=0")
+    if clip_vision is None or image is None:
+        raise ValueError(f"{FEATURE}: without embeds= the call needs clip_vision= and image=")
+    which = "penultimate_hidden_states" if info["is_plus"] else "image_embeds"
+    want, have = file_clip_width(model, info), clip_vision.output_width[which]
+    if want != have:
+        raise NotImplementedError(f"{FEATURE}: the file's clip_embeddings_dim is {want}, this CLIP-vision tower's {which} are {have} wide: "
+                                  "the file was made for another image encoder")
+    from .clipvision import clip_preprocess
+    image = image.to(clip_vision.load_device)
+    rows = clip_preprocess(image)
+    if not info["is_plus"]:
+        e = clip_vision.encode_pixel_rows(rows)[which]
+        return e, torch.zeros_like(e)
+    b = image.shape[0]
+    black = clip_preprocess(torch.zeros(b, 224, 224, 3, device=image.device))
+    both = clip_vision.encode_pixel_rows(torch.cat([rows, black]))[which]
+    return both[:b].contiguous(), both[b:].contiguous()
+
+
+def patch_ipadapter(unet_patcher, ipadapter_sd, embeds=None, weight=1.0, weight_type="original", start_at=0.0, end_at=1.0, attn_mask=None, unfold_batch=False,
+                    clip_vision=None, image=None, noise=0.0):
     """-> a clone of `unet_patcher` that applies the IP-Adapter file `ipadapter_sd` (the loaded .bin / .pth / .safetensors state dict) on
     embeds = (clip_embed, clip_embed_zeroed), the reference's own `embeds=` argument of apply_ipadapter: CLIP-vision image_embeds [1, D] for base
-    files, penultimate_hidden_states [1, 257, D] for plus files.  The clone carries the transformer option "ipadapter" (the native route), or --
+    files, penultimate_hidden_states [1, 257, D] for plus files.  With embeds=None they are computed from `image` ([b, h, w, 3] in [0, 1]) by
+    `clip_vision` (embeds_from_image); `embeds` may also be the reference's preprocessor dict (clip_vision, image, weight_type, noise, embeds,
+    unfold_batch), whose entries then stand for the keyword arguments of the same names.  The clone carries the transformer option "ipadapter" (the native route), or --
     with attn_mask, unfold_batch, more than one reference image, more than 4 units or more than 64 tokens in all -- the same arithmetic as Python
     attn2 replace patches.  Refused (NotImplementedError, before any launch): Flux; FaceID / FaceID-Plus / Portrait / InstantID and 'full' files;
     a file whose to_k_ip count does not fit the UNet; native Perturbed-Attention Guidance or ControlNet-LLLite, or Python block hooks, on the
@@ -337,9 +375,18 @@ def patch_ipadapter(unet_patcher, ipadapter_sd, embeds, weight, weight_type="ori
     from ..modules.k_model import KModelFlux
     if isinstance(unet_patcher.model, KModelFlux):
         raise NotImplementedError(f"{FEATURE}: UNet models only (Flux has no cross-attention against a text context to extend)")
+    if isinstance(embeds, dict):
+        unknown = sorted(set(embeds) - set(PREPROCESSOR_KEYS))
+        if unknown:
+            raise ValueError(f"{FEATURE}: the preprocessor dict has keys {unknown}; known: {PREPROCESSOR_KEYS}")
+        d = embeds
+        clip_vision, image, embeds = d.get("clip_vision", clip_vision), d.get("image", image), d.get("embeds")
+        weight_type, noise, unfold_batch = d.get("weight_type", weight_type), d.get("noise", noise), d.get("unfold_batch", unfold_batch)
     model = nets.split_file(ipadapter_sd)
     info = nets.detect(model)
     nets.refuse_unsupported(model, info)
+    if embeds is None:
+        embeds = embeds_from_image(clip_vision, image, model, info, noise)
     to = unet_patcher.model_options.get("transformer_options", {})
     if unet_patcher.model_options.get("pag") is not None:
         raise NotImplementedError(f"{FEATURE} with native Perturbed-Attention Guidance on the same job: its third row group has no image tokens")
@@ -385,7 +432,8 @@ class IPAdapterPatcher:
         self.weight_type = "original"
 
     def process_before_every_sampling(self, process, cond, mask=None, *args, **kwargs):
-        """cond: the unit's embeddings (clip_embed, clip_embed_zeroed) -- the CLIP-vision encoder is the caller's"""
+        """cond: the unit's embeddings (clip_embed, clip_embed_zeroed), or the reference's preprocessor dict (clip_vision, image, weight_type,
+        noise, embeds, unfold_batch): with embeds=None in it the embeddings are computed from the image (patch_ipadapter)"""
         objs = process.sd_model.forge_objects
         objs.unet = patch_ipadapter(objs.unet, self.state_dict, cond, self.strength, self.weight_type, self.start_percent, self.end_percent,
                                     attn_mask=mask)

@@ -752,6 +752,38 @@ def embed_tokens(ids, tok_emb, pos_emb, out=None):
     return out
 
 
+CLIP_IMAGE, CLIP_PATCH_COLS, CLIP_TOKENS = (_lib.CLIPVISION_CONSTANTS[n] for n in ("FMXV_CLIP_IMAGE", "FMXV_CLIP_PATCH_COLS", "FMXV_CLIP_TOKENS"))
+
+
+def clip_patch_rows(image, top, left, out=None):
+    """image fp32 [b, 3, rh, rw] (NCHW, after the resize) -> fp16 [b * 256, 640]: the 224 x 224 window at (top, left) quantised to 8-bit levels,
+    normalised with CLIP's mean / std and laid out as the rows of the 14 x 14 patch convolution (fmxv_clip_patch_rows_f16, include/fmx_clipvision.h)"""
+    if not image.is_cuda or image.dtype != torch.float32 or image.dim() != 4 or image.shape[1] != 3 or not image.is_contiguous():
+        raise TypeError(f"clip_patch_rows expects a contiguous fp32 device tensor [b, 3, h, w], got {image.dtype} {tuple(image.shape)} on {image.device}")
+    b, _, rh, rw = image.shape
+    if out is None:
+        out = empty((b * 256, CLIP_PATCH_COLS), torch.float16, image.device)
+    _check_f16(out)
+    assert out.is_contiguous() and out.numel() == b * 256 * CLIP_PATCH_COLS
+    _call("fmxv_clip_patch_rows_f16", _p(image), _p(out), b, rh, rw, int(top), int(left))
+    return out
+
+
+def clip_embed_ln(patches, class_embedding, position_embedding, gamma, beta, *, eps=1e-5, rows_per_image=320, out=None):
+    """patches fp16 [b * 256, c] -> fp16 [b * rows_per_image, c]: per image LN(class + pos[0]), LN(patches[p] + pos[1 + p]) for the 256 patches,
+    then zero rows up to rows_per_image (fmxv_clip_embed_ln_f16, include/fmx_clipvision.h)"""
+    _check_f16(patches, class_embedding, position_embedding, gamma, beta, out)
+    c = patches.shape[-1]
+    b = patches.shape[0] // 256
+    assert patches.is_contiguous() and patches.shape[0] == b * 256 and position_embedding.is_contiguous() and tuple(position_embedding.shape) == (CLIP_TOKENS, c)
+    assert class_embedding.numel() == c and gamma.numel() == c and beta.numel() == c
+    if out is None:
+        out = empty((b * rows_per_image, c), torch.float16, patches.device)
+    assert out.is_contiguous() and out.numel() == b * rows_per_image * c
+    _call("fmxv_clip_embed_ln_f16", _p(patches), _p(class_embedding), _p(position_embedding), _p(gamma), _p(beta), _p(out), b, c, int(rows_per_image), float(eps))
+    return out
+
+
 def cast_f16(x, out=None):
     if out is None:
         out = empty(x.shape, torch.float16, x.device)

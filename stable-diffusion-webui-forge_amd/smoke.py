@@ -74,4 +74,10 @@ def run():
             bad.append((key, rms, pp))
     print(f"smoke: {len(outs)} UNet layers against the rounding oracle, layer by layer: worst rms_rel {worst_rms:.2e}, worst per-pixel {worst_pp:.2e}")
     assert len(outs) > 100 and not bad, f"layer-wise parity outside the sharp gate: {bad[:4]}"
+    # the CLIP-vision encoder (backend/patcher/clipvision.py): a seeded 224 x 224 image through the tiny tower with heads of 80
+    from forge_amd.backend.patcher.clipvision import ClipVisionModel
+    vcfg = synth.TINY_CLIP_VISION_CONFIGS["d80"]
+    emb = ClipVisionModel(vcfg, synth.synth_clip_vision_state_dict(vcfg), "cuda:0").encode_image(synth.synth_image(224, 224, 5)).image_embeds
+    assert bool(torch.isfinite(emb).all())
+    print("smoke: clip-vision image_embeds rms %.4f" % float(emb.pow(2).mean().sqrt()))
     print("smoke OK")

@@ -382,6 +382,87 @@ def synth_clip_state_dict(cfg, seed=4, **kw):
     return synth_state_dict(clip_param_shapes(cfg), seed=seed, **kw)
 
 
+# CLIP-vision towers (backend/nn/clip_vision.py): tiny twins with the three real head widths -- 64 (ViT-L/14, quick_gelu), 80 (ViT-H/14) and 104
+# (ViT-bigG/14) -- at the real image / patch size; projection 64 = IPADAPTER_CLIP_DIM, so the tiny IP-Adapter files take their image_embeds
+def _tiny_clip_vision(hidden, heads, act):
+    return dict(hidden_size=hidden, intermediate_size=2 * hidden, num_hidden_layers=2, num_attention_heads=heads, hidden_act=act, projection_dim=64,
+                image_size=224, patch_size=14, num_channels=3, layer_norm_eps=1e-5)
+
+
+TINY_CLIP_VISION_CONFIGS = {"d64": _tiny_clip_vision(128, 2, "quick_gelu"), "d80": _tiny_clip_vision(320, 4, "gelu"), "d104": _tiny_clip_vision(832, 8, "gelu")}
+
+
+def clip_vision_param_shapes(cfg):
+    """transformers' CLIPVisionModelWithProjection keys: vision_model.* and visual_projection.weight"""
+    c, f = cfg["hidden_size"], cfg["intermediate_size"]
+    s = OrderedDict()
+    p = "vision_model."
+    s[p + "embeddings.class_embedding"] = (c,)
+    s[p + "embeddings.patch_embedding.weight"] = (c, cfg.get("num_channels", 3), cfg.get("patch_size", 14), cfg.get("patch_size", 14))
+    s[p + "embeddings.position_embedding.weight"] = ((cfg.get("image_size", 224) // cfg.get("patch_size", 14)) ** 2 + 1, c)
+    s[p + "pre_layrnorm.weight"], s[p + "pre_layrnorm.bias"] = (c,), (c,)
+    for i in range(cfg["num_hidden_layers"]):
+        b = f"{p}encoder.layers.{i}."
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            s[b + f"self_attn.{n}.weight"], s[b + f"self_attn.{n}.bias"] = (c, c), (c,)
+        for n in ("layer_norm1", "layer_norm2"):
+            s[b + n + ".weight"], s[b + n + ".bias"] = (c,), (c,)
+        s[b + "mlp.fc1.weight"], s[b + "mlp.fc1.bias"] = (f, c), (f,)
+        s[b + "mlp.fc2.weight"], s[b + "mlp.fc2.bias"] = (c, f), (c,)
+    s[p + "post_layernorm.weight"], s[p + "post_layernorm.bias"] = (c,), (c,)
+    s["visual_projection.weight"] = (cfg["projection_dim"], c)
+    return s
+
+
+def synth_clip_vision_state_dict(cfg, seed=17, embed_gain=0.5, mlp_gain=(1.5, 4.0)):
+    """random-init CLIP-vision tower, a pure function of (name, shape, seed): projections around the init law (N(0, 1) * DEFAULT_GAIN / sqrt(fan_in),
+    biases on their weight's fan_in), every LayerNorm 1 + 0.1 N / 0.1 N, class and position embeddings N(0, embed_gain^2) -- of the order of the
+    patch projection's output, so that leaving either out is visible.  mlp_gain = (fc1, fc2) factors on the MLP's two projections: at the init law's
+    own gain the pre-activations are so small that erf-GELU and quick-GELU differ by 4 x the fp16 floor of the output; at (1.5, 4) they differ by 12 x"""
+    shapes = clip_vision_param_shapes(cfg)
+    sd = OrderedDict()
+    for name, shape in shapes.items():
+        z = torch.from_numpy(np.random.Generator(np.random.PCG64([seed, zlib.crc32(name.encode())])).standard_normal(shape, dtype=np.float32))
+        if "norm" in name:
+            z = 1.0 + 0.1 * z if name.endswith(".weight") else 0.1 * z
+        elif "embeddings.class_embedding" in name or "position_embedding" in name:
+            z = embed_gain * z
+        else:
+            wshape = shapes[name[:-5] + ".weight"] if name.endswith(".bias") else shape
+            z = z * float((mlp_gain[0] if ".mlp.fc1." in name else mlp_gain[1] if ".mlp.fc2." in name else 1.0) * DEFAULT_GAIN / np.sqrt(int(np.prod(wshape[1:]))))
+        sd[name] = z
+    return sd
+
+
+def openclip_keyed(sd, prefix="visual."):
+    """a transformers-keyed CLIP-vision state dict in OpenCLIP's layout (what backend/patcher/clipvision.convert_to_transformers reads): q / k / v
+    fused into attn.in_proj_*, ln_pre / ln_post, conv1, positional_embedding, proj = visual_projection.weight transposed"""
+    top = {"vision_model.embeddings.class_embedding": "class_embedding", "vision_model.embeddings.patch_embedding.weight": "conv1.weight",
+           "vision_model.embeddings.position_embedding.weight": "positional_embedding", "vision_model.post_layernorm.weight": "ln_post.weight",
+           "vision_model.post_layernorm.bias": "ln_post.bias", "vision_model.pre_layrnorm.weight": "ln_pre.weight", "vision_model.pre_layrnorm.bias": "ln_pre.bias"}
+    block = {"layer_norm1": "ln_1", "layer_norm2": "ln_2", "mlp.fc1": "mlp.c_fc", "mlp.fc2": "mlp.c_proj", "self_attn.out_proj": "attn.out_proj"}
+    out = OrderedDict()
+    for k, v in sd.items():
+        if k in top:
+            out[prefix + top[k]] = v
+        elif k == "visual_projection.weight":
+            out[prefix + "proj"] = v.t().contiguous()
+        else:
+            i, rest = k[len("vision_model.encoder.layers."):].split(".", 1)
+            mod, leaf = rest.rsplit(".", 1)
+            if mod == "self_attn.q_proj":
+                b = f"vision_model.encoder.layers.{i}.self_attn."
+                out[f"{prefix}transformer.resblocks.{i}.attn.in_proj_{leaf}"] = torch.cat([sd[f"{b}{p}_proj.{leaf}"] for p in "qkv"])
+            elif mod in block:
+                out[f"{prefix}transformer.resblocks.{i}.{block[mod]}.{leaf}"] = v
+    return out
+
+
+def synth_image(h, w, seed, batch=1):
+    """uniform-random fp32 image [batch, h, w, 3] in [0, 1) (the reference's BHWC image tensors)"""
+    return torch.from_numpy(np.random.Generator(np.random.PCG64([seed, 3])).random((batch, h, w, 3), dtype=np.float32))
+
+
 # T5-XXL as Flux uses it (backend/huggingface/black-forest-labs/FLUX.1-dev/text_encoder_2/config.json): 24 layers, 64 heads of 64, gated tanh-GELU
 T5_XXL_CONFIG = dict(d_model=4096, d_ff=10240, num_layers=24, num_heads=64, vocab_size=32128, dense_act_fn="gelu_pytorch_tanh", is_gated_act=True, model_type="t5")
 TINY_T5_CONFIG = dict(d_model=128, d_ff=320, num_layers=3, num_heads=2, vocab_size=1000, dense_act_fn="gelu_pytorch_tanh", is_gated_act=True, model_type="t5")

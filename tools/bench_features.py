@@ -18,6 +18,9 @@ batch sizes -- and what they cost.
                                                      attn1 / attn2 patches on the hooked executor, and the adapter launches on their own
     python tools/bench_features.py --only ipadapter  IP-Adapter: plain / native with a base file, a plus file and two units (dual attention kernel,
                                                      captured graph) / the composite route forced / the same units as Python attn2 replace patches
+    python tools/bench_features.py --only clipvision CLIP-vision encode_image of 2 images at 512 x 768 on synthetic full-size ViT-H/14 and ViT-bigG/14: native against
+                                                     transformers' CLIPVisionModelWithProjection in fp16 on the same GPU; the routes are primed, then timed alternately
+                                                     in one process, median of 5 -> profiles/clipvision_native_vs_torch.jsonl (--out), with the share of the two new kernels
     python tools/bench_features.py --only taesd      the TAESD decode of batch x (res/8)^2 SDXL-shaped latents (synthetic weights, fp16) next to the Full
                                                      VAE decode of the same latents in the same process: median of 5 after warm-up, events around the calls
 """
@@ -74,6 +77,76 @@ def taesd_leg(batch, width, height, dev):
                       "taesd_out": list(img.shape)}), flush=True)
 
 
+def clipvision_leg(dev, out_path, images=2, height=512, width=768):
+    """encode_image, native against transformers in fp16, on synthetic full-size towers (module docstring)"""
+    from transformers import CLIPVisionConfig, CLIPVisionModelWithProjection
+    from forge_amd import hipops as ops
+    from forge_amd.backend.patcher import clipvision as cv
+    g = torch.Generator(device=dev).manual_seed(11)
+    image = torch.rand(images, height, width, 3, generator=g, device=dev)
+    mean, std = (torch.tensor(v, device=dev).view(3, 1, 1) for v in ((0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)))
+
+    def torch_preprocess(img):
+        x = img.movedim(-1, 1)
+        rh, rw, top, left = cv.preprocess_geometry(x.shape[2], x.shape[3])
+        x = torch.nn.functional.interpolate(x, size=(rh, rw), mode="bicubic", antialias=True)[:, :, top:top + 224, left:left + 224]
+        return ((torch.clip(255.0 * x, 0, 255).round() / 255.0 - mean) / std).half()
+
+    def event_ms(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b), out
+
+    lines = []
+    for family, cfg in (("ViT-H/14", cv.CLIP_VISION_H), ("ViT-bigG/14", cv.CLIP_VISION_G)):
+        sd = {}
+        for name, shape in synth.clip_vision_param_shapes(cfg).items():
+            z = torch.randn(shape, generator=g, device=dev)
+            if "norm" in name:
+                z = 1.0 + 0.1 * z if name.endswith(".weight") else 0.1 * z
+            elif "class_embedding" in name or "position_embedding" in name:
+                z = 0.5 * z
+            else:
+                fan = shape if not name.endswith(".bias") else synth.clip_vision_param_shapes(cfg)[name[:-5] + ".weight"]
+                z = z * (float(synth.DEFAULT_GAIN) / float(torch.tensor(fan[1:]).prod()) ** 0.5)
+            sd[name] = z.half()
+        native = cv.ClipVisionModel(cfg, sd, dev)
+        with torch.device(dev):
+            ref = CLIPVisionModelWithProjection(CLIPVisionConfig(**{k: v for k, v in cfg.items()})).half().eval()
+        ref.load_state_dict(sd, strict=False)
+        del sd
+        routes = {"native": lambda: native.encode_image(image).image_embeds,
+                  "torch_fp16": lambda: ref(pixel_values=torch_preprocess(image), output_hidden_states=True).image_embeds.float()}
+        with torch.inference_mode():
+            outs = {k: [fn() for _ in range(2)][-1] for k, fn in routes.items()}          # primed
+            ms = {k: [] for k in routes}
+            for _ in range(5):
+                for k, fn in routes.items():                                              # alternately
+                    ms[k].append(event_ms(fn)[0])
+            x, top, left = cv.resized(image)
+            rows = ops.clip_patch_rows(x, top, left)
+            patches = ops.linear(rows, native.tower.w["patch"])
+            w = native.tower.w
+            k1 = sorted(event_ms(lambda: ops.clip_patch_rows(x, top, left))[0] for _ in range(5))[2]
+            k2 = sorted(event_ms(lambda: ops.clip_embed_ln(patches, w["class"], w["pos"], *w["pre"], rows_per_image=320))[0] for _ in range(5))[2]
+        med = {k: sorted(v)[2] for k, v in ms.items()}
+        d = (outs["native"].double() - outs["torch_fp16"].double())
+        lines.append({"case": "clip-vision encode_image", "family": family, "images": images, "size": [height, width], "dtype": "f16", "native_ms": round(med["native"], 3),
+                      "torch_fp16_ms": round(med["torch_fp16"], 3), "torch_over_native": round(med["torch_fp16"] / med["native"], 2),
+                      "clip_patch_rows_ms": round(k1, 4), "clip_embed_ln_ms": round(k2, 4), "new_kernels_share_of_native": round((k1 + k2) / med["native"], 4),
+                      "native_vs_torch_rms_rel": float(d.pow(2).mean().sqrt() / outs["torch_fp16"].double().pow(2).mean().sqrt()),
+                      "finite": bool(torch.isfinite(outs["native"]).all()), "src": __import__("forge_amd")._lib.build_info()["src"]})
+        print(json.dumps(lines[-1]), flush=True)
+        del native, ref, routes, outs
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.writelines(json.dumps(ln) + "\n" for ln in lines)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=6)
@@ -83,8 +156,13 @@ def main():
     ap.add_argument("--height", type=int, default=0)
     ap.add_argument("--only", default="samplers,controlnet,hooks,freeu,and,hires")
     ap.add_argument("--pag-routes", default="plain,pag_native,pag_python", help="the routes of --only pag (one route alone for a kernel trace of it)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "clipvision_native_vs_torch.jsonl"), help="where --only clipvision writes its lines")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
+    if "clipvision" in a.only.split(","):
+        clipvision_leg(dev, a.out)
+        if a.only == "clipvision":
+            return
     width, height = a.width or a.res, a.height or a.res
     if "taesd" in a.only.split(","):
         taesd_leg(a.batch, width, height, dev)
