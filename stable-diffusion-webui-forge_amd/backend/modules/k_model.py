@@ -9,10 +9,9 @@ import torch
 
 from ... import hipops as ops
 from ...runtime import HipGraph
-from ..patcher.kohya_hrfix import shrink_for_step, shrink_graph_key
-from ..patcher.ipadapter import FEATURE as IPADAPTER_FEATURE, ipadapter_for_call, units_of as ipadapter_units_of
-from ..patcher.lllite import FEATURE as LLLITE_FEATURE, lllite_for_call, lllite_graph_key, lllite_of
-from ..patcher.stylealign import OPTION as STYLEALIGN, group_size_of_call, share_for_call, share_graph_key
+from ..patcher.freeu import freeu_graph_key  # noqa: F401  (its callers find it here)
+from ..patcher.native_call import PLAIN, check, graph_key, refuse_off_unet, resolve_call, static_key
+from ..patcher.stylealign import OPTION as STYLEALIGN, group_size_of_call
 
 
 class SigmaInfo:
@@ -31,11 +30,6 @@ def tensor_version(t):
         return t._version
     except RuntimeError:
         return -1
-
-
-def freeu_graph_key(freeu):
-    """what native FreeU adds to a graph key: ("freeu", b1, b2, s1, s2)"""
-    return ("freeu",) + tuple(float(v) for v in freeu[:4])
 
 
 def host_sigmas(sigma):
@@ -91,53 +85,17 @@ class KModel:
         return entries
 
     def _forward_static(self, key, x, sigma_dev, sig_host, reps, ctxc, control=None, transformer_options=None, c_concat=None, control_plan=None,
-                        freeu=None, shrink=None, pag_from=None, share=None, lllite=None, ipadapter=None):
+                        native=PLAIN):
         """pack -> [ControlNets ->] UNet -> (returns eps view); static buffers per shape so the chain can be graph-replayed.
         `reps`: the stacked copies of the batch: 1, 2 ([uncond ; cond]) or, with the perturbed group of native Perturbed-Attention Guidance
-        behind them, 2 or 3; `pag_from`: the first image of that group (backend/nn/unet.py), or None.  Such a call arrives with ("pag",) in `key`,
-        so its static buffers and its graph are its own: the steps inside and outside the PAG window of one job are two graphs.
-        `freeu`: the job's native FreeU parameters (transformer_options["freeu_v2"], backend/patcher/freeu.py) or None.  They are launch
-        arguments of the captured kernels, so they are part of the graph key: the steps inside and outside the FreeU window of one job
-        are two graphs.
-        `shrink`: the job's native Kohya HRFix parameters (transformer_options["kohya_hrfix"], backend/patcher/kohya_hrfix.py) when this step's
-        host sigma lies inside their window, else None.  A shrunk forward launches other kernels on other shapes, so it is part of the graph
-        key as well; a step outside the window replays the plain graph.
-        `share`: the call's native StyleAlign (transformer_options["stylealign"], backend/patcher/stylealign.py: images per group, mode, strength)
-        or None.  Such a call arrives with ("stylealign", mode, strength) in `key`: other attention launches, and the blend weights are launch
-        arguments, so its static buffers and its graph are its own.
-        `lllite`: the job's native ControlNet-LLLite unit (transformer_options["lllite"], backend/patcher/lllite.py) when this MODEL CALL lies inside
-        its window -- the caller advanced the unit's call counter -- else None.  Such a call arrives with ("lllite", unit, strength) in `key`: the
-        blocks that have modules launch other kernels; a call outside the window is the plain call on the plain graph.
-        `ipadapter`: the prepared ExtraContext of native IP-Adapter (transformer_options["ipadapter"], backend/patcher/ipadapter.py) when this
-        step's host sigma lies inside the window of at least one unit, else None.  Such a call arrives with the context's graph key in `key` --
-        the active set of units, each unit's identity, weight and weight type, the group order: the cached image K / V^T are captured addresses,
-        the weights launch arguments -- so the steps inside and outside a window are two graphs; outside, the call is the plain call."""
-        if ipadapter is not None:     # refused before any launch
-            if self.diffusion_model._hooks(transformer_options) is not None:
-                raise NotImplementedError(f"{IPADAPTER_FEATURE} (native) together with Python block hooks in transformer_options")
-            if pag_from is not None or lllite is not None:
-                raise NotImplementedError(f"{IPADAPTER_FEATURE} with native Perturbed-Attention Guidance or ControlNet-LLLite on the same job")
-        if share is not None and self.diffusion_model._hooks(transformer_options) is not None:     # refused before any launch
-            raise NotImplementedError("StyleAlign (native) together with Python block hooks in transformer_options")
-        if lllite is not None:     # refused before any launch
-            if self.diffusion_model._hooks(transformer_options) is not None:
-                raise NotImplementedError(f"{LLLITE_FEATURE} (native) together with Python block hooks in transformer_options")
-            if pag_from is not None or share is not None or shrink is not None:
-                raise NotImplementedError(f"{LLLITE_FEATURE} with native Perturbed-Attention Guidance, StyleAlign or Kohya HRFix on the same job")
-            lllite.prepare()       # the cond embeddings, once per unit and outside any capture
-        if pag_from is not None:     # refused before any launch
-            if shrink is not None:
-                raise NotImplementedError("Perturbed-Attention Guidance and Kohya HRFix on the same step: the degraded pass of the reference runs "
-                                          "through the shrink patches as well; that combination has no native route")
-            if control is not None or control_plan:
-                raise NotImplementedError("Perturbed-Attention Guidance with a ControlNet / T2I-Adapter chain: the chain has no third group of rows")
-            if self.diffusion_model._hooks(transformer_options) is not None:
-                raise NotImplementedError("Perturbed-Attention Guidance (native) together with Python block hooks in transformer_options")
-        if shrink is not None:
-            if freeu is not None:
-                raise NotImplementedError("Kohya HRFix and native FreeU on one job: FreeU needs h and the skip at one size, and the two do not commute")
-            if control is not None or any(e["active"] for e in control_plan or ()):
-                raise NotImplementedError("Kohya HRFix with ControlNet / T2I-Adapter residuals: their sizes do not fit the shrunk hidden state")
+        behind them, 2 or 3.  `key`: the caller's base key (batch, channels, h, w, CFG halves[, "pag" | "apply"]).
+        `native`: the call's NativeCall (backend/patcher/native_call.py: what each field does and why it sits in which key); static_key of it
+        joins the key of the static buffers, graph_key of it the graph's."""
+        net = self.diffusion_model
+        hooks = net._hooks(transformer_options)
+        check(native, hooks, chain=control is not None or bool(control_plan),      # refused before any launch
+              residuals=control is not None or any(e["active"] for e in control_plan or ()))
+        key = key + static_key(native)
         b, c, hh, ww = x.shape
         bu = reps * b
         st = self._static.get(key)
@@ -156,19 +114,12 @@ class KModel:
             st["t"].fill_(float(tvals[0]))
         else:
             st["t"].copy_(tvals, non_blocking=False)
-        net = self.diffusion_model
-        hooks = net._hooks(transformer_options)
         concat_term = net.prepare_concat(c_concat, bu) if c_concat is not None else None  # cached per c_concat tensor: once per job
         if not self.use_graph or control is not None or hooks is not None:
             # Python hooks cannot be captured, and a ControlNet chain that needs Python per step arrives here with its residuals: eager
-            return net.forward_packed(st["xcol"], st["t"], ctxc, bu, hh, ww, control, hooks, concat_term, freeu=freeu, shrink=shrink,
-                                      pag_from=pag_from, share=share, lllite=lllite, ipadapter=ipadapter)
+            return net.forward_packed(st["xcol"], st["t"], ctxc, bu, hh, ww, control, hooks, concat_term, native=native)
         active = [e for e in control_plan if e["active"]] if control_plan else []
-        gkey = key if not active else key + ("control",) + tuple(e["cm"].exec_serial for e in active)
-        if freeu is not None:
-            gkey = gkey + freeu_graph_key(freeu)
-        if shrink is not None:
-            gkey = gkey + shrink_graph_key(shrink)
+        gkey = (key if not active else key + ("control",) + tuple(e["cm"].exec_serial for e in active)) + graph_key(native)
 
         def run():
             # The ControlNet trunks read the SAME packed input and timestep buffers as the UNet (both are `calculate_input` of x and the
@@ -178,8 +129,7 @@ class KModel:
             for e in reversed(active):
                 outs = e["cm"].forward_static(st["xcol"], st["t"], e["ctxc"], bu, hh, ww, e["gh"])
                 ctrl = e["cn"].control_merge(None, outs, ctrl, torch.float32)
-            return net.forward_packed(st["xcol"], st["t"], ctxc, bu, hh, ww, control=ctrl, concat_term=concat_term, freeu=freeu, shrink=shrink,
-                                      pag_from=pag_from, share=share, lllite=lllite, ipadapter=ipadapter)
+            return net.forward_packed(st["xcol"], st["t"], ctxc, bu, hh, ww, control=ctrl, concat_term=concat_term, native=native)
 
         def validity():
             # What a captured graph points at: the executors' arenas (re-allocated when a larger shape comes through, e.g. the hires pass),
@@ -250,17 +200,11 @@ class KModel:
                                          float(pag_scale))
         b, c, hh, ww = x.shape
         reps = 1 if uncond_ctx is None else 2
-        job_options = transformer_options
-        freeu = (transformer_options or {}).get("freeu_v2")   # native, no Python hook: stays on the graph path
-        share = share_for_call(transformer_options, b)        # native StyleAlign: the `reps` row groups of b images each
-        if share is not None and self.diffusion_model._hooks(transformer_options) is not None:
-            raise NotImplementedError("StyleAlign (native) together with Python block hooks in transformer_options")
-        # native ControlNet-LLLite: the window is tested here, on the host, once per model call (the unit's call counter advances)
-        lllite = lllite_for_call(transformer_options, self.diffusion_model._hooks(transformer_options),
-                                 (("StyleAlign", (transformer_options or {}).get(STYLEALIGN)), ("Kohya HRFix", (transformer_options or {}).get("kohya_hrfix"))))
-        if self.diffusion_model._hooks(transformer_options) is not None or control_model is not None:
+        cond_or_uncond = [1, 0] if reps == 2 else [0]          # batch order [uncond ; cond] (sampling_function.py:187-229)
+        sig_host = host_sigmas(sigma)
+        native, hooks = resolve_call(transformer_options, b, reps, sig_host, cond_or_uncond, self.diffusion_model)
+        if hooks is not None or control_model is not None:
             to = dict(transformer_options or {})
-            cond_or_uncond = [1, 0] if reps == 2 else [0]          # batch order [uncond ; cond] (sampling_function.py:187-229)
             to["cond_or_uncond"] = cond_or_uncond[:]
             to["sigmas"] = sigma
             to["cond_mark"] = torch.tensor([float(cx) for cx in cond_or_uncond for _ in range(b)], dtype=sigma.dtype, device=sigma.device)
@@ -270,21 +214,11 @@ class KModel:
         else:
             transformer_options = None
         per_call_options = transformer_options
-        sig_host = host_sigmas(sigma)
-        shrink = shrink_for_step(job_options, sig_host)    # native as well; the window is tested on the host's copy of sigma
-        # native IP-Adapter: the units whose window holds this step's host sigma, their image K / V^T prepared (outside any capture)
-        ipadapter = ipadapter_for_call(job_options, sig_host[0], [1, 0] if reps == 2 else [0], reps * b, self.diffusion_model,
-                                       self.diffusion_model._hooks(job_options), (("ControlNet-LLLite", lllite_of(job_options)),))
         if reps == 2:
             ctx = self._stack_ctx(uncond_ctx, cond_ctx)
         else:
             ctx = cond_ctx
         ctxc = self.diffusion_model.prepare_context(ctx[0], ctx[1])
-        key = (b, c, hh, ww, reps) if share is None else (b, c, hh, ww, reps) + share_graph_key(share)
-        if lllite is not None:
-            key = key + lllite_graph_key(lllite)
-        if ipadapter is not None:
-            key = key + ipadapter.graph_key()
         control, plan = None, None
         if control_model is not None:
             # sampling_function.py:261-268: every ControlNet of the chain sees the per-call options, then one get_control on the stacked batch
@@ -293,14 +227,14 @@ class KModel:
                 p.transformer_options = per_call_options
                 p = p.previous_controlnet
             # a chain that needs no Python per step runs inside the captured graph; otherwise its residuals are computed here, eagerly
-            if self.diffusion_model._hooks(transformer_options) is None:
+            if hooks is None:
                 plan = self._control_plan(control_model, sig_host, reps * b, hh, ww, ctx, reps)
             if plan is None:
                 t_all = torch.cat([sigma] * reps)
                 t_all.fmx_sigma = SigmaInfo(list(sig_host) * reps)
                 control = control_model.get_control(torch.cat([x] * reps), t_all, {"c_crossattn": ctx[0], "y": ctx[1]}, reps)
-        eps = self._forward_static(key, x, sigma, sig_host, reps, ctxc, control=control, transformer_options=transformer_options, c_concat=c_concat,
-                                   control_plan=plan, freeu=freeu, shrink=shrink, share=share, lllite=lllite, ipadapter=ipadapter)
+        eps = self._forward_static((b, c, hh, ww, reps), x, sigma, sig_host, reps, ctxc, control=control, transformer_options=transformer_options,
+                                   c_concat=c_concat, control_plan=plan, native=native)
         cond_pred = torch.empty_like(x) if want_parts else None
         uncond_pred = torch.empty_like(x) if want_parts else None
         den = ops.cfg_combine(eps, eps.shape[-1], x, sigma, reps, cond_scale, None, cond_pred, uncond_pred,
@@ -309,31 +243,17 @@ class KModel:
 
     def _denoise_cfg_pag(self, x, sigma, uncond_ctx, cond_ctx, cond_scale, want_parts, transformer_options, control_model, c_concat, pag_scale):
         """denoise_cfg on a step that applies Perturbed-Attention Guidance.  Everything it cannot carry is refused before any launch."""
-        if control_model is not None:
-            raise NotImplementedError("Perturbed-Attention Guidance with a ControlNet / T2I-Adapter chain: the chain has no third group of rows")
-        if self.diffusion_model._hooks(transformer_options) is not None:
-            raise NotImplementedError("Perturbed-Attention Guidance (native) together with Python block hooks in transformer_options")
-        if lllite_of(transformer_options) is not None:
-            raise NotImplementedError(f"{LLLITE_FEATURE} with native Perturbed-Attention Guidance on the same job")
-        if ipadapter_units_of(transformer_options) is not None:
-            raise NotImplementedError(f"{IPADAPTER_FEATURE} with native Perturbed-Attention Guidance on the same job: its third row group has no image tokens")
-        sig_host = host_sigmas(sigma)
-        shrink = shrink_for_step(transformer_options, sig_host)
-        if shrink is not None:
-            raise NotImplementedError("Perturbed-Attention Guidance and Kohya HRFix on the same step: the degraded pass of the reference runs "
-                                      "through the shrink patches as well; that combination has no native route")
-        if not self.has_middle_attention():
-            out = self.denoise_cfg(x, sigma, uncond_ctx, cond_ctx, cond_scale, want_parts, transformer_options, None, c_concat)
-            return out + (None,) if want_parts else out
         b, c, hh, ww = x.shape
         has_uncond = uncond_ctx is not None
         groups = 3 if has_uncond else 2
+        sig_host = host_sigmas(sigma)
+        native, _ = resolve_call(transformer_options, b, groups, sig_host, None, self.diffusion_model, pag_step=True, chain=control_model is not None)
+        if not self.has_middle_attention():
+            out = self.denoise_cfg(x, sigma, uncond_ctx, cond_ctx, cond_scale, want_parts, transformer_options, None, c_concat)
+            return out + (None,) if want_parts else out
         ctx = self._stack_ctx_pag(uncond_ctx, cond_ctx)
         ctxc = self.diffusion_model.prepare_context(ctx[0], ctx[1])
-        share = share_for_call(transformer_options, b)        # native StyleAlign: the perturbed group is one more share group outside the middle
-        key = (b, c, hh, ww, groups - 1, "pag") if share is None else (b, c, hh, ww, groups - 1, "pag") + share_graph_key(share)
-        eps = self._forward_static(key, x, sigma, sig_host, groups, ctxc, c_concat=c_concat, freeu=(transformer_options or {}).get("freeu_v2"),
-                                   pag_from=(groups - 1) * b, share=share)
+        eps = self._forward_static((b, c, hh, ww, groups - 1, "pag"), x, sigma, sig_host, groups, ctxc, c_concat=c_concat, native=native)
         cond_pred = torch.empty_like(x) if want_parts else None
         uncond_pred = torch.empty_like(x) if want_parts else None
         degraded = torch.empty_like(x) if want_parts else None
@@ -379,30 +299,15 @@ class KModel:
 
     def apply_model(self, x, t, c_concat=None, c_crossattn=None, control=None, transformer_options=None, y=None, **kwargs):
         """Reference signature (k_model.py:25): x fp32 [Bu,C,H,W], t = sigma [Bu] -> denoised fp32."""
-        share = None
-        if (transformer_options or {}).get(STYLEALIGN) is not None:
-            # native StyleAlign: the groups are the entries of cond_or_uncond; refused before any launch when they are unknown or repeat
-            share = share_for_call(transformer_options, group_size_of_call(transformer_options, x.shape[0]))
-            if share is not None and self.diffusion_model._hooks(transformer_options) is not None:
-                raise NotImplementedError("StyleAlign (native) together with Python block hooks in transformer_options")
-        lllite = lllite_for_call(transformer_options, self.diffusion_model._hooks(transformer_options),
-                                 (("StyleAlign", (transformer_options or {}).get(STYLEALIGN)), ("Kohya HRFix", (transformer_options or {}).get("kohya_hrfix"))))
+        to = transformer_options or {}
+        # the row groups are the entries of the caller's cond_or_uncond; native StyleAlign is refused when they are unknown or repeat
+        b = group_size_of_call(to, x.shape[0]) if to.get(STYLEALIGN) is not None else x.shape[0]
+        sig_host = host_sigmas(t)
+        native, _ = resolve_call(to, b, x.shape[0] // b, sig_host, to.get("cond_or_uncond"), self.diffusion_model)
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
         sigma = t.to(device=self.device, dtype=torch.float32).contiguous()
         ctxc = self.diffusion_model.prepare_context(c_crossattn, y)
-        b, c, hh, ww = x.shape
-        sig_host = host_sigmas(t)
-        key = (b, c, hh, ww, 1, "apply") if share is None else (b, c, hh, ww, 1, "apply") + share_graph_key(share)
-        if lllite is not None:
-            key = key + lllite_graph_key(lllite)
-        # native IP-Adapter: the groups are the entries of the caller's cond_or_uncond; refused before any launch when they are unknown or repeat
-        ipadapter = ipadapter_for_call(transformer_options, sig_host[0], (transformer_options or {}).get("cond_or_uncond"), b, self.diffusion_model,
-                                       self.diffusion_model._hooks(transformer_options), (("ControlNet-LLLite", lllite_of(transformer_options)),))
-        if ipadapter is not None:
-            key = key + ipadapter.graph_key()
-        eps = self._forward_static(key, x, sigma, sig_host, 1, ctxc, control, transformer_options, c_concat,
-                                   freeu=(transformer_options or {}).get("freeu_v2"), shrink=shrink_for_step(transformer_options, sig_host),
-                                   share=share, lllite=lllite, ipadapter=ipadapter)
+        eps = self._forward_static(tuple(x.shape) + (1, "apply"), x, sigma, sig_host, 1, ctxc, control, transformer_options, c_concat, native=native)
         return ops.cfg_combine(eps, eps.shape[-1], x, sigma, 1, 1.0, prediction_type=self.predictor.prediction_type,
                                sigma_data=self.predictor.sigma_data)
 
@@ -424,16 +329,7 @@ class KModelFlux:
         return 0
 
     def apply_model(self, x, t, c_concat=None, c_crossattn=None, control=None, transformer_options=None, y=None, guidance=None, **kwargs):
-        if (transformer_options or {}).get("freeu_v2") is not None:
-            raise NotImplementedError("FreeU: UNet models only")   # the reference's script declines models without model_channels
-        if (transformer_options or {}).get("kohya_hrfix") is not None:
-            raise NotImplementedError("Kohya HRFix: UNet models only")
-        if (transformer_options or {}).get("stylealign") is not None:
-            raise NotImplementedError("StyleAlign: UNet models only")
-        if lllite_of(transformer_options) is not None:
-            raise NotImplementedError(f"{LLLITE_FEATURE}: UNet models only")
-        if ipadapter_units_of(transformer_options) is not None:
-            raise NotImplementedError(f"{IPADAPTER_FEATURE}: UNet models only")
+        refuse_off_unet(transformer_options)
         if c_concat is not None or control is not None:
             raise NotImplementedError("c_concat / control are outside the txt2img hot path")
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
@@ -446,16 +342,7 @@ class KModelFlux:
 
     def denoise_cfg(self, x, sigma, uncond_ctx, cond_ctx, cond_scale, want_parts=False, transformer_options=None, control_model=None):
         to = transformer_options or {}
-        if to.get("freeu_v2") is not None:
-            raise NotImplementedError("FreeU: UNet models only")
-        if to.get("kohya_hrfix") is not None:
-            raise NotImplementedError("Kohya HRFix: UNet models only")
-        if to.get("stylealign") is not None:
-            raise NotImplementedError("StyleAlign: UNet models only")
-        if lllite_of(to) is not None:
-            raise NotImplementedError(f"{LLLITE_FEATURE}: UNet models only")
-        if ipadapter_units_of(to) is not None:
-            raise NotImplementedError(f"{IPADAPTER_FEATURE}: UNet models only")
+        refuse_off_unet(transformer_options)
         if control_model is not None or to.get("patches") or to.get("patches_replace") or to.get("block_modifiers"):
             raise NotImplementedError("ControlNet / per-block hooks are built for the LDM UNet executor, not for the Flux transformer")
         ctx, y, guidance = cond_ctx

@@ -31,6 +31,7 @@ import torch
 from ... import hipops as ops
 from ..._lib import knob as _knob
 from ...runtime import Arena, ArenaOverflow
+from ..patcher.native_call import PLAIN, NativeCall, check
 from .layout import ConvIn, Down, Res, SpatialT, Up, unet_layout
 
 SUPPORTED_DPAD = (48, 64, 80, 160)
@@ -456,17 +457,20 @@ class IntegratedUNet2DConditionModel:
         outs = ops.lllite_adapt(x, None, n, [None if s is None else dict(s, cond=lllite.cond_emb(s)) for s in slots], lllite.strength)
         return [x if o is None else o for o in outs]
 
-    def _attn_block(self, b, L, h, bu, n, ctxc, arena, rs1=None, want_next=False, pag_from=None, share=None, lllite=None, ipadapter=None):
+    def _attn_block(self, b, L, h, bu, n, ctxc, arena, rs1=None, want_next=False, native=PLAIN):
         """One BasicTransformerBlock on h [M, C] (updated in place).  rs1: the row statistics the projection that WROTE h left (proj_in or the
         previous block's ff.net.2) -- norm1 then runs folded into the q|k and V^T projections; want_next: leave the statistics of this block's
-        output for the next block's norm1.  pag_from: see _self_attention (everything but the attention itself runs on all rows).
+        output for the next block's norm1.  native: the call's NativeCall (backend/patcher/native_call.py), of which this block reads
+        pag_from: see _self_attention (everything but the attention itself runs on all rows).
         share: None, or native StyleAlign (backend/patcher/stylealign.py Share): the self-attention of every group of share.b images runs over
         their joined tokens ("aligned"), or is blended with the ordinary one ("blend", ops.attn_blend); see _shared_attention.  What governs the
         projections is then the token count of a group, T = b * n: tile-aligned T runs them dense (and folded) even where n alone is ragged.
         lllite: None, or the native ControlNet-LLLite unit of this call (backend/patcher/lllite.py) when THIS block has modules: the norm in front
         of an attention that has modules runs unfolded (its statistics rs1 / rs2 are not consumed), one ops.lllite_adapt makes the operands of
         to_q / to_k / to_v, and the three projections read them separately; norm3 and the next block's norm1 fold as ever.
+        ipadapter: see _cross_attention.
         -> that RowStats (or None)."""
+        pag_from, share, lllite, ipadapter = native.pag_from, native.share, native.lllite, native.ipadapter
         H, d = L.heads, L.dim_head
         dp = _dpad(d)
         hd = H * dp
@@ -688,8 +692,9 @@ class IntegratedUNet2DConditionModel:
             return h
         return r.permute(0, 2, 3, 1).to(torch.float16).contiguous()
 
-    def _spatial_transformer(self, L, x, ctxc, arena, to=None, pag_from=None, share=None, lllite=None, ipadapter=None):
+    def _spatial_transformer(self, L, x, ctxc, arena, to=None, native=PLAIN):
         k = L.key
+        share, lllite = native.share, native.lllite
         bu, hh, ww, c = x.shape
         n = hh * ww
         inner = L.heads * L.dim_head
@@ -698,8 +703,6 @@ class IntegratedUNet2DConditionModel:
         mk = arena.mark()
         g = ops.groupnorm(x, *self.w[k + ".norm"], 1e-6)
         hooked = to is not None and (to.get("patches") or to.get("patches_replace"))
-        if hooked and pag_from is not None:
-            raise NotImplementedError("Perturbed-Attention Guidance (native) together with Python transformer patches")
         # norm1 of every block folded into its q|k / V^T projections: the GEMM that writes h (proj_in, then each block's ff.net.2) leaves the row sums
         # (under native StyleAlign the attention sequence is a group's b * n tokens: that count decides, as in _attn_block)
         fold1 = _LN_FOLD and _LN_FOLD1 and not hooked and (n if share is None else share.b * n) % 64 == 0 and (f"{k}.transformer_blocks.0.attn1.v.ln") in self.w
@@ -717,8 +720,7 @@ class IntegratedUNet2DConditionModel:
             else:
                 bk = f"{k}.transformer_blocks.{di}"
                 rs1 = self._attn_block(bk, L, h, bu, n, ctxc, arena, rs1=rs1, want_next=fold1 and di + 1 < L.depth and not ll_attn1(di + 1),
-                                       pag_from=pag_from, share=share, lllite=lllite if lllite is not None and bk in lllite.blocks else None,
-                                       ipadapter=ipadapter)
+                                       native=native if lllite is None or bk in lllite.blocks else native._replace(lllite=None))
             self._tap(f"{k}.transformer_blocks.{di}", h.view(bu, n, -1))
         _, st = ops.linear(h, *self.w[k + ".proj_out"], residual=x.view(-1, c), out=out.view(-1, c), ld_out=c, n=bu, h=hh, w=ww, stats=True,
                            stats_partial=out_part)
@@ -747,7 +749,7 @@ class IntegratedUNet2DConditionModel:
             return Upsample(key=L.key)
         return Conv2d(key=L.key)
 
-    def _run_block(self, blk, h, skip, emb_all, ctxc, arena, up_to=None, to=None, pag_from=None, share=None, lllite=None, ipadapter=None):
+    def _run_block(self, blk, h, skip, emb_all, ctxc, arena, up_to=None, to=None, native=PLAIN):
         inner = to.get("block_inner_modifiers", []) if to is not None else []
         wrapper = to.get("group_norm_wrapper") if to is not None else None
         standins = TimestepEmbedSequential(self._layer_standin(L) for L in blk) if inner else None
@@ -769,7 +771,7 @@ class IntegratedUNet2DConditionModel:
                 h = self._res(L, h, skip, emb_all, arena)
                 skip = None
             elif isinstance(L, SpatialT):
-                h = self._spatial_transformer(L, h, ctxc, arena, to, pag_from, share, lllite, ipadapter)
+                h = self._spatial_transformer(L, h, ctxc, arena, to, native)
                 if to is not None and "transformer_index" in to:
                     to["transformer_index"] += 1  # unet.py:82-84
             elif isinstance(L, Down):
@@ -872,69 +874,27 @@ class IntegratedUNet2DConditionModel:
                                           "its Python patches")
             lllite.check_rows(b, n, bu)
 
-    def _forward_impl(self, xcol, t, ctxc, bu, hh, ww, arena, control=None, to=None, concat_term=None, freeu=None, shrink=None, pag_from=None,
-                      share=None, lllite=None, ipadapter=None):
+    def _forward_impl(self, xcol, t, ctxc, bu, hh, ww, arena, control=None, to=None, concat_term=None, native=PLAIN):
         """xcol: [Bu*H*W, 64] im2col of the (scaled) input; t: [Bu] fp32 table indices.  -> eps [Bu*H*W, out_ch].
         `to`: transformer_options with Python hooks (unet.py:696-763 hook points), or None on the fast path.
-        `freeu`: a FreeUParams tuple (b1, b2, s1, s2, ...) of backend/patcher/freeu.py, or None: native FreeU v2 on the inputs of the
-        output blocks whose h has 4x / 2x model_channels channels.  Not a Python hook: it runs on the fast path and inside a captured graph.  It
-        runs where the reference's output_block_patch runs when FreeU is the first installed patch; a job that ALSO installs Python
-        output-block patches gets native FreeU first, then those patches, eagerly as before.
-        `shrink`: a KohyaHRFixParams tuple of backend/patcher/kohya_hrfix.py, or None: native Kohya HRFix (Deep Shrink).  After input block
-        `block_number` h is resized to round(extent / factor) -- after the skip is stored, or before it (downscale_after_skip False) -- and at every
-        output block whose popped skip has another height h is resized to the skip's size, where the reference's input_block_patch(_after_skip)
-        and output_block_patch run (kohya_hrfix.py:13-28).  Not a Python hook either: fast path, captured graph; Python patches of the same
-        job run after it.  The caller decides the sigma window (KModel hands the option over only inside it).
-        `pag_from`: None, or the first image of the perturbed group of native Perturbed-Attention Guidance (backend/patcher/pag.py; KModel stacks
-        [uncond ; cond ; cond] and hands over 2b, or b without uncond).  The images from there on get V as the self-attention output of EVERY
-        transformer block of the middle block -- the reference's patches_replace key ("middle", 0) carries no block index, so it matches all of
-        them (attention.py / unet.py:201-214) -- and run like the others everywhere else.  Fast path, captured graph.
-        `share`: None, or native StyleAlign (backend/patcher/stylealign.py Share(b, mode, strength); KModel hands it over for groups of b > 1 images):
-        in EVERY transformer block of every level the self-attention of each group of b consecutive images runs over the group's joined tokens
-        (the reference's set_model_replace_all(attn1_proc, "attn1")); attn2 is untouched.  With `pag_from` the perturbed group keeps V in the middle
-        block (the degraded pass replaces ("middle", 0) itself) and is one more group everywhere else.  Fast path, captured graph.
-        `lllite`: None, or the native ControlNet-LLLite unit (backend/patcher/lllite.py LLLite) of a call inside its window: the transformer blocks
-        it has modules for adapt the inputs of their q / k / v projections (_attn_block).  Fast path, captured graph.
-        `ipadapter`: None, or the prepared ExtraContext of native IP-Adapter (backend/patcher/ipadapter.py) for a call inside a unit's window: every
-        cross-attention adds the units' image-token attention to the text attention (_cross_attention).  Fast path, captured graph."""
-        if ipadapter is not None:     # refused before any launch
-            from ..patcher.ipadapter import FEATURE as IPADAPTER, check_cond_or_uncond
-            if to is not None:
-                raise NotImplementedError(f"{IPADAPTER} (native) together with Python block hooks in transformer_options")
-            if pag_from is not None:
-                raise NotImplementedError(f"{IPADAPTER} with native Perturbed-Attention Guidance on the same job: its third row group has no image tokens")
-            if lllite is not None:
-                raise NotImplementedError(f"{IPADAPTER} with native ControlNet-LLLite on the same job")
-            check_cond_or_uncond(ipadapter.cond_or_uncond, bu)
-        if lllite is not None:     # refused before any launch
-            from ..patcher.lllite import FEATURE as LLLITE
-            if to is not None:
-                raise NotImplementedError(f"{LLLITE} (native) together with Python block hooks in transformer_options")
-            if share is not None or pag_from is not None or shrink is not None:
-                raise NotImplementedError(f"{LLLITE} with native Perturbed-Attention Guidance, StyleAlign or Kohya HRFix on the same job")
-            self._lllite_check(lllite, bu, hh, ww)
+        `native`: the call's NativeCall (backend/patcher/native_call.py: what each field makes this walk do).  Everything is refused before
+        any launch: what cannot run together by native_call's rules, then what is wrong with a field's value."""
+        residuals = control is not None and any(len(v) > 0 for v in control.values())
+        check(native, to, chain=residuals, residuals=residuals)
+        freeu, shrink, pag_from, share = native.freeu, native.shrink, native.pag_from, native.share
+        if native.ipadapter is not None:
+            from ..patcher.ipadapter import check_cond_or_uncond
+            check_cond_or_uncond(native.ipadapter.cond_or_uncond, bu)
+        if native.lllite is not None:
+            self._lllite_check(native.lllite, bu, hh, ww)
         if share is not None:
             if share.b < 2 or bu % share.b != 0 or (pag_from is not None and pag_from % share.b != 0):
                 raise ValueError(f"StyleAlign groups of {share.b} images do not tile the batch of {bu} (perturbed group from {pag_from})")
             if share.mode not in ("aligned", "blend"):
                 raise ValueError(f"StyleAlign mode {share.mode!r}")
-            if to is not None:
-                raise NotImplementedError("StyleAlign (native) together with Python block hooks in transformer_options")
-        if pag_from is not None:
-            if not 0 < pag_from < bu:
-                raise ValueError(f"pag_from {pag_from} outside the batch of {bu}")
-            if to is not None:
-                raise NotImplementedError("Perturbed-Attention Guidance (native) together with Python block hooks in transformer_options")
-            if shrink is not None:
-                raise NotImplementedError("Perturbed-Attention Guidance and Kohya HRFix on the same step")
-            if control is not None and any(len(v) > 0 for v in control.values()):
-                raise NotImplementedError("Perturbed-Attention Guidance with ControlNet / T2I-Adapter residuals: the chain has no third group of rows")
-        if shrink is not None:
-            if freeu is not None:
-                raise NotImplementedError("Kohya HRFix and native FreeU on one job: FreeU needs h and the skip at one size, and the two do not commute")
-            if control is not None and any(len(v) > 0 for v in control.values()):
-                # the reference prints a warning and drops the residuals whose size no longer fits; a silently dropped ControlNet is refused here
-                raise NotImplementedError("Kohya HRFix with ControlNet / T2I-Adapter residuals: their sizes do not fit the shrunk hidden state")
+        if pag_from is not None and not 0 < pag_from < bu:
+            raise ValueError(f"pag_from {pag_from} outside the batch of {bu}")
+        outside = native._replace(pag_from=None)      # the perturbed group keeps V in the middle block only
         freeu_scales = None
         if freeu is not None:
             b1, b2, s1, s2 = (float(v) for v in freeu[:4])
@@ -988,7 +948,7 @@ class IntegratedUNet2DConditionModel:
                     h = self._call_nchw(m, h, "after", conv_in[0], 0, conv_in, to)
             else:
                 h = modify(h, "before")
-                h = self._run_block(blk, h, None, emb_all, ctxc, arena, to=to, share=share, lllite=lllite, ipadapter=ipadapter)
+                h = self._run_block(blk, h, None, emb_all, ctxc, arena, to=to, native=outside)
             h = self._apply_control(h, control, "input")
             h = modify(h, "after")
             if shrink is not None and bi == shrink.block_number and not shrink.downscale_after_skip:
@@ -1003,7 +963,7 @@ class IntegratedUNet2DConditionModel:
         if to is not None:
             to["block"] = ("middle", 0)
         h = modify(h, "before")
-        h = self._run_block(lay.middle, h, None, emb_all, ctxc, arena, to=to, pag_from=pag_from, share=share, lllite=lllite, ipadapter=ipadapter)
+        h = self._run_block(lay.middle, h, None, emb_all, ctxc, arena, to=to, native=native)
         h = self._apply_control(h, control, "middle")
         h = modify(h, "after")
         for bi, blk in enumerate(lay.output_blocks):
@@ -1033,7 +993,7 @@ class IntegratedUNet2DConditionModel:
                 # halves separate (dual-input GroupNorm / conv), so it is materialised only when a modifier wants to see it
                 cat = modify(torch.cat([h, skip], dim=-1), "before")
                 h, skip = cat[..., :h.shape[-1]].contiguous(), cat[..., h.shape[-1]:].contiguous()
-            h = self._run_block(blk, h, skip, emb_all, ctxc, arena, up_to, to=to, share=share, lllite=lllite, ipadapter=ipadapter)
+            h = self._run_block(blk, h, skip, emb_all, ctxc, arena, up_to, to=to, native=outside)
             h = modify(h, "after")
         if to is not None:
             to["block"] = ("last", 0)
@@ -1077,18 +1037,16 @@ class IntegratedUNet2DConditionModel:
             self.arena_epoch += 1
         return self._arena
 
-    def forward_packed(self, xcol, t, ctxc, bu, hh, ww, control=None, transformer_options=None, concat_term=None, freeu=None, shrink=None,
-                       pag_from=None, share=None, lllite=None, ipadapter=None):
+    def forward_packed(self, xcol, t, ctxc, bu, hh, ww, control=None, transformer_options=None, concat_term=None, native=PLAIN):
         """Hot-path entry (no layout conversion): returns eps as fp16 [Bu*H*W, out_channels] living in the arena
-        (valid until the next forward).  `freeu`, `shrink`: see _forward_impl (the caller takes them out of transformer_options["freeu_v2"] /
-        ["kohya_hrfix"]); `pag_from`, `share`, `lllite`, `ipadapter`: see _forward_impl."""
+        (valid until the next forward).  `native`: the call's NativeCall (backend/patcher/native_call.py)."""
+        hooks = self._hooks(transformer_options)
         while True:
             arena = self._get_arena(bu, hh, ww)
             arena.reset()
             try:
                 with arena:
-                    return self._forward_impl(xcol, t, ctxc, bu, hh, ww, arena, control, self._hooks(transformer_options), concat_term, freeu,
-                                              shrink, pag_from, share, lllite, ipadapter)
+                    return self._forward_impl(xcol, t, ctxc, bu, hh, ww, arena, control, hooks, concat_term, native)
             except ArenaOverflow:
                 torch.cuda.synchronize(self.device)
                 self._arena_bytes = arena.capacity * 2
@@ -1126,8 +1084,8 @@ class IntegratedUNet2DConditionModel:
             x = x[:, :self.latent_channels]
         xcol = ops.unet_pack_input(x.contiguous(), ones, 1, 1.0)
         eps = self.forward_packed(xcol, timesteps.to(device=self.device, dtype=torch.float32).contiguous(), ctxc, bu, hh, ww, control,
-                                  transformer_options, concat_term, freeu=(transformer_options or {}).get("freeu_v2"),
-                                  shrink=(transformer_options or {}).get("kohya_hrfix"))
+                                  transformer_options, concat_term,
+                                  native=NativeCall(freeu=(transformer_options or {}).get("freeu_v2"), shrink=(transformer_options or {}).get("kohya_hrfix")))
         return eps.view(bu, hh, ww, -1).permute(0, 3, 1, 2).to(x.dtype)
 
     __call__ = forward

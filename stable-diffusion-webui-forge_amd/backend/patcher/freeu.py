@@ -9,6 +9,7 @@ from collections import namedtuple
 FreeUParams = namedtuple("FreeUParams", ["b1", "b2", "s1", "s2", "start", "end"], defaults=(0.0, 1.0))
 
 OPTION = "freeu_v2"
+FEATURE = "FreeU"
 
 # name -> (b1, b2, s1, s2, start, end): the presets the reference's UI offers
 PRESETS = {
@@ -45,3 +46,8 @@ def options_for_step(model_options, sampling_step, total_sampling_steps):
     out = dict(model_options)
     out["transformer_options"] = {k: v for k, v in to.items() if k != OPTION}
     return out
+
+
+def freeu_graph_key(freeu):
+    """what native FreeU adds to a graph key: ("freeu", b1, b2, s1, s2)"""
+    return ("freeu",) + tuple(float(v) for v in freeu[:4])

@@ -211,19 +211,13 @@ def check_cond_or_uncond(cond_or_uncond, batch):
         raise NotImplementedError(f"{FEATURE} (native): a batch of {batch} images does not split into {len(cond_or_uncond)} groups")
 
 
-def ipadapter_for_call(transformer_options, sigma, cond_or_uncond, batch, net, hooks=None, companions=()):
+def ipadapter_for_call(transformer_options, sigma, cond_or_uncond, batch, net):
     """One model call on the fused route -> the ExtraContext of the units whose window holds the call's sigma (a host float), prepared, or None
-    (no option, or every unit outside its window: the plain call, the plain graph, bit for bit).  Everything that cannot run beside the native
-    route is refused first, before any launch.  `hooks`: the executor's view of Python block hooks; `companions`: (name, value) of native
-    options of this call that exclude IP-Adapter."""
+    (no option, or every unit outside its window: the plain call, the plain graph, bit for bit).  What cannot run beside the native route is
+    refused before (native_call.resolve_call)."""
     units = units_of(transformer_options)
     if units is None:
         return None
-    if hooks is not None:
-        raise NotImplementedError(f"{FEATURE} (native) together with Python block hooks in transformer_options")
-    for name, value in companions:
-        if value is not None:
-            raise NotImplementedError(f"{FEATURE} with native {name} on the same job")
     check_cond_or_uncond(cond_or_uncond, batch)
     active = [u for u in units if u.active(float(sigma))]
     if not active:
@@ -388,10 +382,11 @@ def patch_ipadapter(unet_patcher, ipadapter_sd, embeds=None, weight=1.0, weight_
     if embeds is None:
         embeds = embeds_from_image(clip_vision, image, model, info, noise)
     to = unet_patcher.model_options.get("transformer_options", {})
+    from .native_call import message
     if unet_patcher.model_options.get("pag") is not None:
-        raise NotImplementedError(f"{FEATURE} with native Perturbed-Attention Guidance on the same job: its third row group has no image tokens")
+        raise NotImplementedError(message("ipadapter", "pag_from"))
     if to.get("lllite") is not None:
-        raise NotImplementedError(f"{FEATURE} with native ControlNet-LLLite on the same job")
+        raise NotImplementedError(message("ipadapter", "lllite"))
     if _has_foreign_hooks(to):
         raise NotImplementedError(f"{FEATURE} together with Python block hooks in transformer_options")
     predictor = unet_patcher.model.predictor

@@ -14,6 +14,7 @@ KohyaHRFixParams = namedtuple("KohyaHRFixParams", ["block_number", "downscale_fa
                                                    "downscale_method", "upscale_method", "sigma_start", "sigma_end"])
 
 OPTION = "kohya_hrfix"
+FEATURE = "Kohya HRFix"
 
 
 def _check_method(name):
@@ -36,7 +37,8 @@ def patch_kohya_hrfix(unet_patcher, block_number=3, downscale_factor=2.0, start_
         raise NotImplementedError("Kohya HRFix: UNet models only")
     predictor = unet_patcher.model.predictor
     if unet_patcher.model_options.get("transformer_options", {}).get("freeu_v2") is not None:
-        raise NotImplementedError("Kohya HRFix and native FreeU on one job: FreeU needs h and the skip at one size, and the two do not commute")
+        from .native_call import message
+        raise NotImplementedError(message("shrink", "freeu"))
     m = unet_patcher.clone()
     m.set_transformer_option(OPTION, KohyaHRFixParams(int(block_number), float(downscale_factor), float(start_percent), float(end_percent),
                                                       bool(downscale_after_skip), downscale_method, upscale_method,

@@ -259,13 +259,14 @@ class PythonPatch:
 
 
 def _refuse_companions(unet_patcher):
+    from .native_call import message
     to = unet_patcher.model_options.get("transformer_options", {})
     if unet_patcher.model_options.get("pag") is not None:
-        raise NotImplementedError(f"{FEATURE} with native Perturbed-Attention Guidance on the same job")
+        raise NotImplementedError(message("lllite", "pag_from"))
     if to.get("stylealign") is not None:
-        raise NotImplementedError(f"{FEATURE} with native StyleAlign on the same job")
+        raise NotImplementedError(message("lllite", "share"))
     if to.get("kohya_hrfix") is not None:
-        raise NotImplementedError(f"{FEATURE} with native Kohya HRFix on the same job: the shrunk blocks have other token counts than the cond embedding")
+        raise NotImplementedError(message("lllite", "shrink"))
 
 
 def _has_foreign_hooks(to):
@@ -313,19 +314,11 @@ def lllite_of(transformer_options):
     return (transformer_options or {}).get(OPTION)
 
 
-def lllite_for_call(transformer_options, hooks=None, companions=()):
+def lllite_for_call(transformer_options):
     """One model call on the fused route -> the LLLite whose adapters apply to it, or None (no option, or outside the window: the plain call, the
-    plain graph).  Advances the call counter; everything that cannot run beside the native route is refused first, before any launch.
-    `hooks`: the executor's view of Python block hooks; `companions`: (name, value) of native options of this call that exclude LLLite."""
+    plain graph).  Advances the call counter, so it runs once per model call and after the call's refusals (native_call.resolve_call)."""
     lll = lllite_of(transformer_options)
-    if lll is None:
-        return None
-    if hooks is not None:
-        raise NotImplementedError(f"{FEATURE} (native) together with Python block hooks in transformer_options")
-    for name, value in companions:
-        if value is not None:
-            raise NotImplementedError(f"{FEATURE} with native {name} on the same job")
-    if not lll.counter.advance():
+    if lll is None or not lll.counter.advance():
         return None
     return lll
 

@@ -34,12 +34,10 @@ def check_batch_coupled_options(model_options, world_size):
     """Images of a batch are independent -- except under a model option that couples them.  Native StyleAlign (backend/patcher/stylealign.py)
     shares self-attention among the images of a batch, so a batch split over more than one rank would shrink its groups: NotImplementedError,
     raised by the sharded entry on every rank before any collective."""
-    from .backend.patcher.stylealign import check_world
-    check_world((model_options or {}).get("transformer_options"), world_size)
-    from .backend.patcher.lllite import check_world as lllite_check_world
-    lllite_check_world((model_options or {}).get("transformer_options"), world_size)    # image i of a call uses control image i % Bc
-    from .backend.patcher.ipadapter import check_world as ipadapter_check_world
-    ipadapter_check_world((model_options or {}).get("transformer_options"), world_size)  # image b of a call reads the tokens of its group
+    from .backend.patcher.native_call import MODULES
+    for m in MODULES.values():      # StyleAlign; ControlNet-LLLite: image i of a call uses control image i % Bc; IP-Adapter: image b reads the tokens of its group
+        if hasattr(m, "check_world"):
+            m.check_world((model_options or {}).get("transformer_options"), world_size)
 
 
 def _flatten(cond):

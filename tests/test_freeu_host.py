@@ -10,6 +10,7 @@ from forge_amd import hipops as ops
 from forge_amd.backend.modules import k_model
 from forge_amd.backend.nn.unet import IntegratedUNet2DConditionModel as UNetExecutor
 from forge_amd.backend.patcher import freeu
+from forge_amd.backend.patcher.native_call import NativeCall
 from forge_amd.backend.patcher.unet import UnetPatcher
 
 from conftest import load_golden
@@ -97,7 +98,7 @@ class _Net:
         self.calls = []
 
     def forward_packed(self, *a, **kw):
-        self.calls.append(kw.get("freeu"))
+        self.calls.append(kw["native"].freeu)
         raise _Reached
 
 
@@ -116,7 +117,7 @@ def test_graph_key_carries_freeu_and_is_unchanged_without_it(monkeypatch):
     key = (1, 4, 8, 8, 2)
     for fu in (None, freeu.FreeUParams(1.3, 1.4, 0.9, 0.2)):
         with pytest.raises(_Reached):
-            km._forward_static(key, x, None, [1.0], 2, ctxc, freeu=fu)
+            km._forward_static(key, x, None, [1.0], 2, ctxc, native=NativeCall(freeu=fu))
     plain, with_freeu = list(km._gstate)
     assert plain == key                                              # today's key, nothing appended
     assert with_freeu == key + ("freeu", 1.3, 1.4, 0.9, 0.2)

@@ -416,7 +416,7 @@ def test_euler_job_on_the_graph_equals_the_job_run_eagerly(fx, monkeypatch):
     count = Counted(monkeypatch, net)
     calls = []
     real_static = km._forward_static
-    monkeypatch.setattr(km, "_forward_static", lambda *a, **kw: (calls.append(kw.get("ipadapter") is not None), real_static(*a, **kw))[1])
+    monkeypatch.setattr(km, "_forward_static", lambda *a, **kw: (calls.append(kw["native"].ipadapter is not None), real_static(*a, **kw))[1])
     km._drop_graphs()
     km._static.clear()
     spec = fx["cases"]["base/original"]

@@ -13,6 +13,7 @@ from forge_amd import hipops as ops  # noqa: E402
 from forge_amd import runtime, synth  # noqa: E402
 from forge_amd.backend.patcher import lllite as ll  # noqa: E402
 from forge_amd.backend.patcher.lllite import patch_lllite  # noqa: E402
+from forge_amd.backend.patcher.native_call import NativeCall  # noqa: E402
 from forge_amd.modules import processing, shared  # noqa: E402
 from forge_amd.modules.prompt_parser import DictWithShape  # noqa: E402
 
@@ -232,7 +233,7 @@ def test_a_block_without_modules_keeps_its_folds():
     lll = ll.LLLite(lsd, L.control_images(1, (hh * 8, ww * 8), 3), 1.0, 0, 0.0, 0.0, DEV)
     assert list(lll.blocks) == [first] and lll.native_ok()
     lll.prepare()
-    eps = net.forward_packed(xcol, t, ctxc, bu, hh, ww, lllite=lll)
+    eps = net.forward_packed(xcol, t, ctxc, bu, hh, ww, native=NativeCall(lllite=lll))
     torch.cuda.synchronize()
     trace = dict(net.fold_trace)
     assert trace[first] == (False, False, True), trace[first]
@@ -268,7 +269,7 @@ def test_euler_job_on_the_graph_equals_the_job_run_eagerly(job, monkeypatch):
     real_hooked, real_launch, real_static = net._attn_block_hooked, runtime.HipGraph.launch, km._forward_static
     monkeypatch.setattr(net, "_attn_block_hooked", lambda *a, **kw: (hooked.append(1), real_hooked(*a, **kw))[1], raising=False)
     monkeypatch.setattr(runtime.HipGraph, "launch", lambda self, s: (launches.append(1), real_launch(self, s))[1])
-    monkeypatch.setattr(km, "_forward_static", lambda *a, **kw: (calls.append(kw.get("lllite") is not None), real_static(*a, **kw))[1])
+    monkeypatch.setattr(km, "_forward_static", lambda *a, **kw: (calls.append(kw["native"].lllite is not None), real_static(*a, **kw))[1])
     km._drop_graphs()
     km._static.clear()
     window = dict(steps=6, start_percent=0.25, end_percent=0.7)
@@ -288,7 +289,7 @@ def test_heun_job_advances_the_counter_per_model_call(job, monkeypatch):
     km = job["km"]
     calls = []
     real_static = km._forward_static
-    monkeypatch.setattr(km, "_forward_static", lambda *a, **kw: (calls.append(kw.get("lllite") is not None), real_static(*a, **kw))[1])
+    monkeypatch.setattr(km, "_forward_static", lambda *a, **kw: (calls.append(kw["native"].lllite is not None), real_static(*a, **kw))[1])
     steps = 4
     run_job(job, unit(job, 1.0, steps=steps, start_percent=0.0, end_percent=0.5), "Heun", steps)
     assert len(calls) > steps, calls

@@ -15,6 +15,7 @@ import forge_amd  # noqa: E402,F401
 from forge_amd import hipops as ops  # noqa: E402
 from forge_amd import synth  # noqa: E402
 from forge_amd.backend.diffusion_engine.base import build_engine  # noqa: E402
+from forge_amd.backend.patcher.native_call import NativeCall  # noqa: E402
 from forge_amd.backend.patcher.pag import patch_pag  # noqa: E402
 from forge_amd.modules import processing, sd_samplers_common, shared  # noqa: E402
 
@@ -146,7 +147,7 @@ def test_perturbed_images_get_v_in_every_middle_block_and_nowhere_else(i):
     keep = 2048          # tokens per image that leave the device (the folded case stores 16384)
     net.tap = lambda name, tens: taps.__setitem__(name, tens[:, :keep].detach().to("cpu", copy=True)) if name.endswith((".attn1.o", ".attn1.v")) else None
     try:
-        net.forward_packed(xcol, t, net.prepare_context(ctx, y), bu, hh, ww, pag_from=2)
+        net.forward_packed(xcol, t, net.prepare_context(ctx, y), bu, hh, ww, native=NativeCall(pag_from=2))
     finally:
         net.tap = None
     torch.cuda.synchronize()

@@ -13,6 +13,7 @@ from forge_amd import hipops as ops  # noqa: E402
 from forge_amd import runtime, synth  # noqa: E402
 from forge_amd.backend.nn.layout import SpatialT  # noqa: E402
 from forge_amd.backend.nn.unet import IntegratedUNet2DConditionModel as UNetExecutor  # noqa: E402
+from forge_amd.backend.patcher.native_call import NativeCall  # noqa: E402
 from forge_amd.backend.patcher.pag import patch_pag  # noqa: E402
 from forge_amd.backend.patcher.stylealign import Share, patch_stylealign  # noqa: E402
 from forge_amd.modules import processing, shared  # noqa: E402
@@ -153,7 +154,7 @@ def tapped_forward(cfg, hh, ww, bu, share, pag_from=None, seed=0):
     wanted = tuple(f".attn{a}.{w}" for a in (1, 2) for w in "qkvo")
     net.tap = lambda name, tens: taps.__setitem__(name, tens.detach().to("cpu", copy=True)) if name.endswith(wanted) else None
     try:
-        net.forward_packed(xcol, t, net.prepare_context(ctx, y), bu, hh, ww, pag_from=pag_from, share=share)
+        net.forward_packed(xcol, t, net.prepare_context(ctx, y), bu, hh, ww, native=NativeCall(pag_from=pag_from, share=share))
     finally:
         net.tap = None
     torch.cuda.synchronize()

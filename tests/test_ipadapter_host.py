@@ -225,7 +225,7 @@ def test_key_order_equals_the_references_hard_coded_lists():
 def test_graph_keys_and_the_window_on_both_sides_of_both_ends(fx, monkeypatch):
     net, km, packs = _kmodel(monkeypatch)
     seen = []
-    net.forward_packed = lambda *a, **kw: (seen.append(kw.get("ipadapter")), (_ for _ in ()).throw(_Reached()))[1]
+    net.forward_packed = lambda *a, **kw: (seen.append(kw["native"].ipadapter), (_ for _ in ()).throw(_Reached()))[1]
     monkeypatch.setattr(ipa.ExtraContext, "prepare", lambda self, net: self)
     x = torch.zeros(2, 4, 32, 32)
     c, uc = (torch.ones(2, 77, 8), None), (torch.zeros(2, 77, 8), None)

@@ -15,6 +15,7 @@ from forge_amd.backend.modules.k_prediction import Prediction
 from forge_amd.backend.nn.unet import IntegratedUNet2DConditionModel as UNetExecutor
 from forge_amd.backend.patcher import kohya_hrfix as kh
 from forge_amd.backend.patcher.freeu import patch_freeu_v2
+from forge_amd.backend.patcher.native_call import NativeCall
 from forge_amd.backend.patcher.unet import UnetPatcher
 
 import kohya_refs as kr
@@ -73,7 +74,7 @@ class _Net:
         return type("C", (), {"key": 1, "serial": 1})()
 
     def forward_packed(self, *a, **kw):
-        self.calls.append(kw.get("shrink"))
+        self.calls.append(kw["native"].shrink)
         raise _Reached
 
 
@@ -158,21 +159,21 @@ def test_patch_kohya_hrfix_defaults_clone_and_refusals(monkeypatch):
     net, km = _kmodel(monkeypatch)
     x, ctxc = torch.zeros(1, 4, 8, 8), net.prepare_context(None, None)
     with pytest.raises(NotImplementedError, match="native FreeU"):
-        km._forward_static((1, 4, 8, 8, 1), x, None, [1.0], 1, ctxc, freeu=both["freeu_v2"], shrink=p)
+        km._forward_static((1, 4, 8, 8, 1), x, None, [1.0], 1, ctxc, native=NativeCall(freeu=both["freeu_v2"], shrink=p))
     with pytest.raises(NotImplementedError, match="native FreeU"):
-        UNetExecutor._forward_impl(None, None, None, None, 1, 8, 8, None, freeu=both["freeu_v2"], shrink=p)
+        UNetExecutor._forward_impl(None, None, None, None, 1, 8, 8, None, native=NativeCall(freeu=both["freeu_v2"], shrink=p))
     # ControlNet / T2I residuals with an active shrink (the reference warns and drops the control): eager residuals, a captured chain, the executor
     residuals = {"input": [], "middle": [torch.zeros(1)], "output": []}
     with pytest.raises(NotImplementedError, match="ControlNet"):
-        km._forward_static((1, 4, 8, 8, 1), x, None, [1.0], 1, ctxc, control=residuals, shrink=p)
+        km._forward_static((1, 4, 8, 8, 1), x, None, [1.0], 1, ctxc, control=residuals, native=NativeCall(shrink=p))
     with pytest.raises(NotImplementedError, match="ControlNet"):
-        km._forward_static((1, 4, 8, 8, 1), x, None, [1.0], 1, ctxc, control_plan=[{"active": True}], shrink=p)
+        km._forward_static((1, 4, 8, 8, 1), x, None, [1.0], 1, ctxc, control_plan=[{"active": True}], native=NativeCall(shrink=p))
     with pytest.raises(NotImplementedError, match="ControlNet"):
-        UNetExecutor._forward_impl(None, None, None, None, 1, 8, 8, None, control=residuals, shrink=p)
+        UNetExecutor._forward_impl(None, None, None, None, 1, 8, 8, None, control=residuals, native=NativeCall(shrink=p))
     assert net.calls == []
     # outside the window the same job runs with its ControlNet: nothing is refused before the executor
     with pytest.raises(_Reached):
-        km._forward_static((1, 4, 8, 8, 1), x, None, [1.0], 1, ctxc, control=residuals, shrink=None)
+        km._forward_static((1, 4, 8, 8, 1), x, None, [1.0], 1, ctxc, control=residuals, native=NativeCall(shrink=None))
 
 
 def test_wrapper_refuses_other_modes_and_layouts_before_the_library(monkeypatch):

@@ -21,6 +21,7 @@ from forge_amd.backend.nn.unet import IntegratedUNet2DConditionModel as UNetExec
 from forge_amd.backend.patcher import lllite as ll
 from forge_amd.backend.patcher.kohya_hrfix import patch_kohya_hrfix
 from forge_amd.backend.patcher.lllite import ControlLLLitePatcher, patch_lllite
+from forge_amd.backend.patcher.native_call import NativeCall
 from forge_amd.backend.patcher.pag import patch_pag
 from forge_amd.backend.patcher.stylealign import patch_stylealign
 from forge_amd.backend.patcher.unet import UnetPatcher
@@ -141,11 +142,11 @@ def test_refusals_at_the_model_call_come_before_any_launch(fx, lsd, monkeypatch)
         km.apply_model(x, sig, c_crossattn=c[0], transformer_options=dict(to, patches={"attn1_output_patch": [lambda o, e: o]}))
     lll = to["lllite"]
     with pytest.raises(NotImplementedError, match="ControlNet-LLLite.*Python block hooks"):
-        km._forward_static((2, 4, 32, 32, 2), x, None, [1.0, 1.0], 2, None, transformer_options={"patches": {"attn1_patch": [len]}}, lllite=lll)
+        km._forward_static((2, 4, 32, 32, 2), x, None, [1.0, 1.0], 2, None, transformer_options={"patches": {"attn1_patch": [len]}}, native=NativeCall(lllite=lll))
     with pytest.raises(NotImplementedError, match="ControlNet-LLLite.*Python block hooks"):
-        UNetExecutor._forward_impl(None, None, None, None, 4, 32, 32, None, to={"patches": {}}, lllite=lll)
+        UNetExecutor._forward_impl(None, None, None, None, 4, 32, 32, None, to={"patches": {}}, native=NativeCall(lllite=lll))
     with pytest.raises(NotImplementedError, match="ControlNet-LLLite with native"):
-        UNetExecutor._forward_impl(None, None, None, None, 4, 32, 32, None, pag_from=2, lllite=lll)
+        UNetExecutor._forward_impl(None, None, None, None, 4, 32, 32, None, native=NativeCall(pag_from=2, lllite=lll))
     assert packs == [] and net.calls == [] and lll.counter.current == 0
     flux = k_model.KModelFlux.__new__(k_model.KModelFlux)
     with pytest.raises(NotImplementedError, match="ControlNet-LLLite: UNet models only"):
@@ -212,7 +213,7 @@ def test_ragged_embeddings_and_a_second_unit_take_the_python_patches(fx, lsd):
 def test_graph_keys_plain_outside_the_window_unit_and_strength_inside(fx, lsd, monkeypatch):
     net, km, packs = _kmodel(monkeypatch)
     seen = []
-    net.forward_packed = lambda *a, **kw: (seen.append(kw.get("lllite")), (_ for _ in ()).throw(_Reached()))[1]
+    net.forward_packed = lambda *a, **kw: (seen.append(kw["native"].lllite), (_ for _ in ()).throw(_Reached()))[1]
     monkeypatch.setattr(ll.LLLite, "prepare", lambda self: None)
     x = torch.zeros(2, 4, 32, 32)
     c, uc = (torch.ones(2, 77, 8), None), (torch.zeros(2, 77, 8), None)

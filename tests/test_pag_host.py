@@ -17,6 +17,9 @@ from forge_amd.backend.nn.unet import IntegratedUNet2DConditionModel as UNetExec
 from forge_amd.backend.patcher import pag
 from forge_amd.backend.patcher.freeu import patch_freeu_v2
 from forge_amd.backend.patcher.kohya_hrfix import patch_kohya_hrfix
+from forge_amd.backend.patcher import native_call as nc
+from forge_amd.backend.patcher.native_call import NativeCall
+from forge_amd.backend.patcher.stylealign import Share
 from forge_amd.backend.patcher.unet import UnetPatcher
 from forge_amd.backend.sampling import sampling_function as sf
 
@@ -231,7 +234,7 @@ class _Net:
         return type("C", (), {"key": 1, "serial": 1})()
 
     def forward_packed(self, *a, **kw):
-        self.calls.append((a[3], kw.get("pag_from"), kw.get("freeu")))
+        self.calls.append((a[3], kw["native"].pag_from, kw["native"].freeu))
         raise _Reached
 
 
@@ -323,16 +326,83 @@ def test_every_refusal_names_the_feature_and_comes_before_any_launch(monkeypatch
     ctxc = net.prepare_context(torch.zeros(3, 77, 8), None)
     p = kohya["kohya_hrfix"]
     residuals = {"input": [], "middle": [torch.zeros(1)], "output": []}
-    for kw, what in ((dict(shrink=p), "Kohya HRFix"), (dict(control=residuals), "ControlNet"), (dict(control_plan=[{"active": True}]), "ControlNet"),
-                     (dict(transformer_options={"patches": {"attn1_patch": [1]}}), "Python block hooks")):
+    pag2 = NativeCall(pag_from=2)
+    for kw, what in ((dict(native=pag2._replace(shrink=p)), "Kohya HRFix"), (dict(control=residuals), "ControlNet"),
+                     (dict(control_plan=[{"active": True}]), "ControlNet"), (dict(transformer_options={"patches": {"attn1_patch": [1]}}), "Python block hooks")):
         with pytest.raises(NotImplementedError, match=name + ".*" + what):
-            km._forward_static((1, 4, 8, 8, 2, "pag"), x, None, [1.0], 3, ctxc, pag_from=2, **kw)
-    for kw, what in ((dict(shrink=p), "Kohya HRFix"), (dict(control=residuals), "ControlNet"), (dict(to={"patches": {}}), "Python block hooks")):
+            km._forward_static((1, 4, 8, 8, 2, "pag"), x, None, [1.0], 3, ctxc, **dict(dict(native=pag2), **kw))
+    for kw, what in ((dict(native=pag2._replace(shrink=p)), "Kohya HRFix"), (dict(control=residuals), "ControlNet"), (dict(to={"patches": {}}), "Python block hooks")):
         with pytest.raises(NotImplementedError, match=name + ".*" + what):
-            UNetExecutor._forward_impl(None, None, None, None, 3, 8, 8, None, pag_from=2, **kw)
+            UNetExecutor._forward_impl(None, None, None, None, 3, 8, 8, None, **dict(dict(native=pag2), **kw))
     with pytest.raises(ValueError, match="pag_from"):
-        UNetExecutor._forward_impl(None, None, None, None, 3, 8, 8, None, pag_from=3)
+        UNetExecutor._forward_impl(None, None, None, None, 3, 8, 8, None, native=NativeCall(pag_from=3))
     assert len(packs) == 1 and len(net.calls) == 1
+
+
+# ---- the exclusion table: KModel, the executor and the table itself refuse the same calls with the same words -----------------------------------------
+_HOOKED = {"patches": {"attn1_patch": [len]}}
+_RESIDUALS = {"input": [], "middle": [torch.zeros(1)], "output": []}
+
+
+def _field_values():
+    """a value for every field of the record that gets a batch of 2 x 2 images past the executor's own value checks"""
+    return dict(freeu=patch_freeu_v2(_patcher(), 1.3, 1.4, 0.9, 0.2).model_options["transformer_options"]["freeu_v2"],
+                shrink=patch_kohya_hrfix(_patcher(), 3, 2.0, 0.0, 1.0).model_options["transformer_options"]["kohya_hrfix"],
+                pag_from=2, share=Share(2, "blend", 0.5), lllite=SimpleNamespace(serial=1, strength=1.0),
+                ipadapter=SimpleNamespace(cond_or_uncond=[1, 0], graph_key=lambda: ("ipadapter", 1)))
+
+
+class _Walk:
+    """`self` of _forward_impl for a call that gets past every refusal: the first thing the walk itself touches says so"""
+    @property
+    def layout(self):
+        raise _Reached
+
+    def _lllite_check(self, *a):
+        raise _Reached
+
+
+def _three_levels(km, native, hooks, control):
+    x, ctxc = torch.zeros(2, 4, 8, 8), type("C", (), {"key": 1, "serial": 1})()
+    return (lambda: nc.check(native, hooks, chain=control is not None, residuals=control is not None),
+            lambda: km._forward_static((2, 4, 8, 8, 2), x, None, [1.0, 1.0], 2, ctxc, control=control, transformer_options=hooks, native=native),
+            lambda: UNetExecutor._forward_impl(_Walk(), None, None, None, 4, 8, 8, None, control=control, to=hooks, native=native))
+
+
+@pytest.mark.parametrize("field, excluded, text", nc.RULES, ids=[f"{f}-{e}" for f, e, _ in nc.RULES])
+def test_a_call_that_breaks_one_rule_is_refused_with_the_rules_words_at_every_level(field, excluded, text, monkeypatch):
+    values = _field_values()
+    native = NativeCall(**{k: values[k] for k in (field, excluded) if k in values})
+    hooks = _HOOKED if excluded == nc.HOOKS else None
+    control = _RESIDUALS if excluded in (nc.CHAIN, nc.RESIDUALS) else None
+    present = dict(native._asdict(), hooks=hooks, chain=control, residuals=control)
+    assert [r for r in nc.RULES if present[r[0]] is not None and present[r[1]] is not None] == [(field, excluded, text)]     # this rule and no other
+    net, km, packs = _kmodel(monkeypatch)
+    for level in _three_levels(km, native, hooks, control):
+        with pytest.raises(NotImplementedError) as e:
+            level()
+        assert str(e.value) == text
+    assert packs == [] and net.calls == [] and km._static == {}                                                           # before any launch
+    assert nc.message(field, excluded) == text
+
+
+def test_a_call_that_breaks_no_rule_passes_every_level(monkeypatch):
+    v = _field_values()
+    fine = (nc.PLAIN, NativeCall(freeu=v["freeu"], pag_from=2, share=v["share"]), NativeCall(shrink=v["shrink"], share=v["share"], ipadapter=v["ipadapter"]),
+            NativeCall(freeu=v["freeu"], lllite=v["lllite"]), NativeCall(freeu=v["freeu"], ipadapter=v["ipadapter"]))
+    for native in fine:
+        net, km, packs = _kmodel(monkeypatch)
+        by_table, by_kmodel, by_executor = _three_levels(km, native, None, None)
+        assert by_table() is None
+        for level in (by_kmodel, by_executor):
+            with pytest.raises(_Reached):
+                level()
+        assert len(packs) == 1 and len(net.calls) == 1
+    # hooks and residuals alone break nothing either: the plain call runs them eagerly
+    net, km, packs = _kmodel(monkeypatch)
+    assert nc.check(nc.PLAIN, _HOOKED, chain=True, residuals=True) is None
+    with pytest.raises(_Reached):
+        km._forward_static((2, 4, 8, 8, 2), torch.zeros(2, 4, 8, 8), None, [1.0, 1.0], 2, None, control=_RESIDUALS, transformer_options=_HOOKED)
 
 
 # ---- the C entry points -----------------------------------------------------------------------------------------------------------------------------

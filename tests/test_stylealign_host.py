@@ -15,6 +15,7 @@ from forge_amd.backend.modules import k_model
 from forge_amd.backend.nn.unet import IntegratedUNet2DConditionModel as UNetExecutor
 from forge_amd.backend.patcher import stylealign as sa
 from forge_amd.backend.patcher.freeu import patch_freeu_v2
+from forge_amd.backend.patcher.native_call import NativeCall
 from forge_amd.backend.patcher.stylealign import patch_stylealign
 from forge_amd.backend.patcher.unet import UnetPatcher
 
@@ -84,12 +85,12 @@ def test_python_hooks_together_with_the_native_option_are_refused(monkeypatch):
     with pytest.raises(NotImplementedError, match="StyleAlign.*Python block hooks"):
         km.apply_model(torch.zeros(6, 4, 8, 8), _sigma(), c_crossattn=torch.zeros(6, 77, 8), transformer_options=dict(hooked, cond_or_uncond=[1, 0]))
     with pytest.raises(NotImplementedError, match="StyleAlign.*Python block hooks"):
-        km._forward_static((3, 4, 8, 8, 2), x, None, [1.0], 2, None, transformer_options=hooked, share=sa.Share(3, "blend", 0.5))
+        km._forward_static((3, 4, 8, 8, 2), x, None, [1.0], 2, None, transformer_options=hooked, native=NativeCall(share=sa.Share(3, "blend", 0.5)))
     with pytest.raises(NotImplementedError, match="StyleAlign.*Python block hooks"):
-        UNetExecutor._forward_impl(None, None, None, None, 6, 8, 8, None, to={"patches": {}}, share=sa.Share(3, "blend", 0.5))
+        UNetExecutor._forward_impl(None, None, None, None, 6, 8, 8, None, to={"patches": {}}, native=NativeCall(share=sa.Share(3, "blend", 0.5)))
     for bu, pag_from in ((7, None), (6, 4)):
         with pytest.raises(ValueError, match="StyleAlign groups of 3"):
-            UNetExecutor._forward_impl(None, None, None, None, bu, 8, 8, None, pag_from=pag_from, share=sa.Share(3, "aligned", 1.0))
+            UNetExecutor._forward_impl(None, None, None, None, bu, 8, 8, None, native=NativeCall(pag_from=pag_from, share=sa.Share(3, "aligned", 1.0)))
     assert packs == [] and net.calls == []
 
 
@@ -144,7 +145,7 @@ def test_every_extension_entry_point_is_named_in_a_gpu_test():
 def test_graph_keys_carry_mode_and_strength_and_b1_is_the_plain_key(monkeypatch):
     net, km, packs = _kmodel(monkeypatch)
     seen = []
-    net.forward_packed = lambda *a, **kw: (seen.append((a[3], kw.get("pag_from"), kw.get("share"))), (_ for _ in ()).throw(_Reached()))[1]
+    net.forward_packed = lambda *a, **kw: (seen.append((a[3], kw["native"].pag_from, kw["native"].share)), (_ for _ in ()).throw(_Reached()))[1]
     c3, uc3 = (torch.ones(3, 77, 8), None), (torch.zeros(3, 77, 8), None)
     x3, x1 = torch.zeros(3, 4, 8, 8), torch.zeros(1, 4, 8, 8)
 

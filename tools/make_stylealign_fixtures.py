@@ -239,7 +239,7 @@ def record_plain(path):
     import inspect
     import stylealign_refs as sr
     from forge_amd.backend.nn.unet import IntegratedUNet2DConditionModel
-    if "share" in inspect.signature(IntegratedUNet2DConditionModel.forward_packed).parameters:
+    if {"share", "native"} & set(inspect.signature(IntegratedUNet2DConditionModel.forward_packed).parameters):     # loose, or inside the NativeCall
         raise SystemExit("this executor already takes `share`: record the plain bits from the commit before it")
     out = [sr.plain_forward(i) for i in range(len(sr.PLAIN_FORWARDS))]
     again = [sr.plain_forward(i) for i in range(len(sr.PLAIN_FORWARDS))]
